@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """Headline benchmark: Matcha-TTS training step on synthetic LJSpeech-shaped batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is
+given (DIR/losses.npy: the step's [dur, prior, diff, total]; DIR/params.npy: the parameters it left, in
+model.parameters() order, a fixed seeded sample when they exceed the size cap) and prints the headline line.
+Every other leg below (roofline, maximum_path, graph-replay profile, extra configurations, precision check,
+synthesise, data-parallel tail, cpu_baseline) runs only with --full; the --no-* options trim a --full run.
 
 `bench.py --gpus N` (N > 1) run without a launcher starts the N ranks itself: before any GPU call it runs
 torch.distributed.run as a child process (one rank per GPU, 127.0.0.1, a free port) and exits with the
@@ -16,7 +22,8 @@ one process per GPU, data parallel over RCCL.  By default the whole step is one 
 replay (N>1: the graph also holds the bucketed RCCL all-reduces, forked off as backward completes
 each bucket -- matcha/dp.py -- then clip+AdamW on the averaged flat gradients);
 --no-graph runs it eagerly under DDP.  Inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line: value = utterances/s over all ranks (max-over-ranks wall time), plus
+Rank 0 prints ONE JSON line: value = utterances/s over all ranks (max-over-ranks wall time), ms_per_step = the
+wall time of one timed step; with --full also
   roofline      the dominant kernel (decoder conv_gemm_kernel): HIP events around each of its launches
                 on the launch stream during one extra eager fwd+bwd after the timed region;
   maximum_path  Mcells/s and roofline_mas (HIP events around maximum_path on the batch's own lattice);
@@ -238,6 +245,26 @@ def graph_replay_profile(args) -> dict:
             "step_busy_us": round(busy, 1), "top_kernels_us": {k: round(v, 1) for k, v in top}}
 
 
+DUMP_MAX_FLOATS = 12 * 2 ** 20  # params.npy stays under 48 MiB (the whole dump under 64 MB)
+
+
+def dump_outputs(out_dir: str, losses: torch.Tensor, model: torch.nn.Module) -> None:
+    """What a caller of the timed path holds after its last step: the step's logged losses
+    [dur, prior, diff, total] and the parameters the update left (float32, model.parameters() order,
+    flattened).  Above DUMP_MAX_FLOATS the parameters are a fixed sample (sorted indices from a seeded
+    generator), so two builds dump the same elements."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "losses.npy", losses.detach().float().cpu().numpy())
+    flat = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()]).cpu().numpy()
+    if flat.size > DUMP_MAX_FLOATS:
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, DUMP_MAX_FLOATS, replace=False))
+        flat = flat[idx]
+    np.save(d / "params.npy", flat)
+
+
 def _free_port() -> int:
     import socket
 
@@ -265,6 +292,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg (roofline, maximum_path, graph-replay "
+                         "profile, extra configurations, precision check, synthesise, data-parallel tail, "
+                         "cpu_baseline); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32): losses "
+                         "[dur, prior, diff, total] and params (the updated parameters)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--tx", type=int, default=120)
     ap.add_argument("--ty", type=int, default=600)
@@ -293,6 +327,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_spawn_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -398,17 +434,85 @@ def main():
                    "step_ms_min_over_ranks": round(-float(elapsed[1]) / args.steps * 1e3, 3)}
     rank_spread["max_over_min"] = round(float(elapsed[0]) / max(-float(elapsed[1]), 1e-12), 4)
     elapsed = float(elapsed[0].item())
+    step_ms = elapsed / args.steps * 1e3
+    losses = trainer.last_losses.tolist()
+    if args.dump_outputs and rank == 0:  # before any later leg runs the model again
+        dump_outputs(args.dump_outputs, trainer.last_losses, model)
     if wd is not None:
         wd.beat("data-parallel tail measurement", last_step_done=args.warmup + args.steps - 1)
     # the exposed tail bucket: one extra eager fwd+bwd with the reducer armed (every rank, no update)
-    dp_tail = trainer.measure_dp_tail(step_batches(0)) if trainer.reducer is not None else None
+    dp_tail = trainer.measure_dp_tail(step_batches(0)) if args.full and trainer.reducer is not None else None
     if wd is not None:
         wd.beat("after the data-parallel legs (rank-local measurements)", bound_s=wd_bounds["post_s"])
     if args.profile_child:  # under rocprofv3 (graph_replay_profile): the trace is all that is wanted
         return
-    losses = trainer.last_losses.tolist()
     if args.bucketed > 0:  # the per-batch measurements below run on batches[0]'s padded shape
         Tx, Ty = int(batch["x"].shape[1]), int(batch["y"].shape[2])
+    from matcha.models.components import _ops as OPS
+
+    # the headline line: everything a plain run prints (the --full legs below add their keys to it)
+    rec = {
+        "metric": "training utterances/sec (whole node) + maximum_path Mcells/sec, LJSpeech batch=32",
+        "value": round(world * B * args.steps / elapsed, 2),
+        "unit": "utterances/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(step_ms, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if args.precision == "32-true" else "bf16",
+        "data": "synthetic LJSpeech-shaped batches (random tokens/mels, ragged lengths), random-init weights",
+        "config": {"workload": f"MatchaTTS train step (encoder + MAS + CFM decoder fwd/bwd + clip + AdamW), "
+                               f"B={B}/GPU, Tx={Tx}, Ty={Ty}, 80 mels",
+                   "model": "MatchaTTS(n_vocab=150, out_channels=80, hidden_channels=192)",
+                   "global_batch": world * B, "seq_len": Ty, "text_len": Tx, "parallelism": f"dp{world}",
+                   "precision": args.precision, "hip_graph": graph,
+                   "weight_planes": 2 if (args.precision == "bf16-parity" or
+                                          (OPS.weight_split_enabled() and args.precision == "bf16-mixed")) else 1,
+                   **({"text_encoder_forward": OPS.encoder_precision_for_parity() + " (backward bf16)"}
+                      if args.precision == "bf16-parity" else {}),
+                   **({"bucketed_batches": [[int(v) for v in (b["x"].shape[1], b["y"].shape[2],
+                                                                 b["x_lengths"].min(), b["y_lengths"].min())]
+                                            for b in batches],
+                       "bucketed_note": "per batch: padded Tx, padded Ty, min x_len, min y_len "
+                                        "(LengthBucketBatchSampler, collate quanta 32 / 256); corpus maxima "
+                                        f"Tx={args.tx}, Ty={args.ty}; the per-call lines below use batch 0"}
+                      if args.bucketed > 0 else {})},
+        "full": args.full,
+        "losses": [round(v, 5) for v in losses],
+        "dp": None if trainer.reducer is None else {
+            "ranks": int(trainer.reducer.comm.ranks), "transport": type(trainer.reducer.comm).__name__,
+            "backend": trainer.reducer.comm.backend,
+            "rccl_version": getattr(trainer.reducer.comm, "version", None),
+            "shared_gpu": os.environ.get("MTTS_BENCH_SHARED_GPU") == "1",
+            "buckets": len(trainer.reducer.buckets), "bucket_mb": trainer.cfg.bucket_mb,
+            "flat_floats": trainer.reducer.flat.numel(),
+            "overlapped_in_graph": bool(next(iter(trainer._graphs.values()))["overlap"]) if trainer._graphs else None,
+            "rank_step_time": rank_spread,
+            "tail": dp_tail,
+            "agree_shapes": trainer.cfg.agree_shapes,
+            "agree_shapes_note": "on (default): every rank pads to the max padded Tx / Ty over ranks, so all ranks "
+                                 "replay one graph; a rank's losses then depend on its peers' padded lengths "
+                                 "(GroupNorm statistics, conv bias in padded frames -- SURVEY 0.6)",
+            "grad_semantics": "after a step each .grad holds the SUM over ranks; the fused clip + AdamW applies "
+                              "the 1 / world mean (GradBucketReducer.mean_grads() gives DDP's means)",
+            "watchdog": None if wd is None else dict(wd_bounds, exit_code=wd.exit_code)},
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(rec), flush=True)
+        if wd is not None:
+            wd.beat("teardown", bound_s=120.0)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        if wd is not None:
+            wd.stop()
+
+    if not args.full:
+        return finish()
 
     # time maximum_path with HIP events on THIS batch's fp32 lattice (same kernels, same stream),
     # right after the timed region; the step itself runs the fused lattice + DP
@@ -616,7 +720,6 @@ def main():
     mas_ms = sum(a.elapsed_time(b) for a, b in mas_events) / max(len(mas_events), 1)
     cells = B * Tx * Ty
     mas_gbs = 12.0 * cells / (mas_ms * 1e-3) / 1e9
-    step_ms = elapsed / args.steps * 1e3
     flops = decoder_train_flops(B, Ty)
     gemm_peak = FP32_MFMA_TFLOPS if args.precision == "32-true" else BF16_DENSE_TFLOPS
     ridge = gemm_peak * 1e12 / (HBM_PEAK_GBS * 1e9)
@@ -695,35 +798,7 @@ def main():
         "bytes = q, k, v, o (+ dO, dq, dk, dv) once")
 
     if rank == 0:
-        rec = {
-            "metric": "training utterances/sec (whole node) + maximum_path Mcells/sec, LJSpeech batch=32",
-            "value": round(world * B * args.steps / elapsed, 2),
-            "unit": "utterances/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(step_ms, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32" if args.precision == "32-true" else "bf16",
-            "data": "synthetic LJSpeech-shaped batches (random tokens/mels, ragged lengths), random-init weights",
-            "config": {"workload": f"MatchaTTS train step (encoder + MAS + CFM decoder fwd/bwd + clip + AdamW), "
-                                   f"B={B}/GPU, Tx={Tx}, Ty={Ty}, 80 mels",
-                       "model": "MatchaTTS(n_vocab=150, out_channels=80, hidden_channels=192)",
-                       "global_batch": world * B, "seq_len": Ty, "text_len": Tx, "parallelism": f"dp{world}",
-                       "precision": args.precision, "hip_graph": graph,
-                       "weight_planes": 2 if (args.precision == "bf16-parity" or
-                                              (OPS.weight_split_enabled() and args.precision == "bf16-mixed")) else 1,
-                       **({"text_encoder_forward": OPS.encoder_precision_for_parity() + " (backward bf16)"}
-                          if args.precision == "bf16-parity" else {}),
-                       **({"bucketed_batches": [[int(v) for v in (b["x"].shape[1], b["y"].shape[2],
-                                                                     b["x_lengths"].min(), b["y_lengths"].min())]
-                                                for b in batches],
-                           "bucketed_note": "per batch: padded Tx, padded Ty, min x_len, min y_len "
-                                            "(LengthBucketBatchSampler, collate quanta 32 / 256); corpus maxima "
-                                            f"Tx={args.tx}, Ty={args.ty}; the per-call lines below use batch 0"}
-                          if args.bucketed > 0 else {})},
+        rec.update({
             "maximum_path": {"value": round(world * cells / mas_ms / 1e3, 1), "unit": "Mcells/s (whole node)",
                              "ms_per_call": round(mas_ms, 4), "calls": len(mas_events),
                              "fused_prior_maximum_path_ms": round(fused_ms, 4),
@@ -749,36 +824,12 @@ def main():
             "decoder_mfma": {"train_flops_per_step": flops,
                              "achieved_tflops_step": round(flops / (step_ms * 1e-3) / 1e12, 2),
                              "peak_tflops": FP32_MFMA_TFLOPS if args.precision == "32-true" else BF16_DENSE_TFLOPS},
-            "losses": [round(v, 5) for v in losses],
-            "dp": None if trainer.reducer is None else {
-                "ranks": int(trainer.reducer.comm.ranks), "transport": type(trainer.reducer.comm).__name__,
-                "backend": trainer.reducer.comm.backend,
-                "rccl_version": getattr(trainer.reducer.comm, "version", None),
-                "shared_gpu": os.environ.get("MTTS_BENCH_SHARED_GPU") == "1",
-                "buckets": len(trainer.reducer.buckets), "bucket_mb": trainer.cfg.bucket_mb,
-                "flat_floats": trainer.reducer.flat.numel(),
-                "overlapped_in_graph": bool(next(iter(trainer._graphs.values()))["overlap"]) if trainer._graphs else None,
-                "rank_step_time": rank_spread,
-                "tail": dp_tail,
-                "agree_shapes": trainer.cfg.agree_shapes,
-                "agree_shapes_note": "on (default): every rank pads to the max padded Tx / Ty over ranks, so all ranks "
-                                     "replay one graph; a rank's losses then depend on its peers' padded lengths "
-                                     "(GroupNorm statistics, conv bias in padded frames -- SURVEY 0.6)",
-                "grad_semantics": "after a step each .grad holds the SUM over ranks; the fused clip + AdamW applies "
-                                  "the 1 / world mean (GradBucketReducer.mean_grads() gives DDP's means)",
-                "watchdog": None if wd is None else dict(wd_bounds, exit_code=wd.exit_code)},
             "precision_check": precision_check,
             "synthesise": synth,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(B, Tx, Ty, args.cpu_budget)
-        print(json.dumps(rec), flush=True)
-    if wd is not None:
-        wd.beat("teardown", bound_s=120.0)
-    if dist.is_initialized():
-        dist.destroy_process_group()
-    if wd is not None:
-        wd.stop()
+    finish()
 
 
 if __name__ == "__main__":

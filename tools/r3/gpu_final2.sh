@@ -13,7 +13,7 @@ cd /tmp; export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --no-cpu-baseline --no-synth --no-extra --no-graph-profile --steps 10 --warmup 3 > $O/prof.json 2> $O/prof.err; rc=$?
 echo "prof rc=$rc"; [ $rc -ne 0 ] && { tail -20 $O/prof.err; exit $rc; }
 T=$(find $O/prof -name "*kernel_trace.csv" | head -1); python3 $R/tools/step_breakdown.py $T > $O/step.txt; head -32 $O/step.txt
-cd $R && timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; rc=$?
+cd $R && timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?
 echo "bench rc=$rc"; [ $rc -ne 0 ] && { tail -20 $O/bench.err; exit $rc; }
 python -c "
 import json; d=json.load(open('$O/bench.json'))

@@ -8,7 +8,7 @@ tail -2 $O/proto2_tests.log; [ $rc -ne 0 ] && { grep -E "^FAILED|^E  .{0,200}" $
 [ $rc -eq 124 ] || [ $rc -eq 137 ] || [ $rc -eq 134 ] || [ $rc -eq 139 ] && exit $rc
 for i in 1 2; do
   for F in 0 2; do
-    MTTS_WGRAD_FUSED_SUM=$F timeout -k 10 200 python bench.py --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/bench_f$F.$i.json 2>/dev/null || exit $?
+    MTTS_WGRAD_FUSED_SUM=$F timeout -k 10 200 python bench.py --full --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/bench_f$F.$i.json 2>/dev/null || exit $?
     echo "fused=$F run $i: $(python -c "import json,sys; d=json.loads([l for l in open('$O/bench_f$F.$i.json') if l.startswith('{')][-1]); print(d['ms_per_step'])")"
   done
 done

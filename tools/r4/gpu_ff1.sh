@@ -7,7 +7,7 @@ tail -1 $O/tests_ff1_oneplane.log; grep -E "rel err|alignment agreement|FAILED" 
 [ $rc -eq 124 ] || [ $rc -eq 137 ] || [ $rc -eq 134 ] || [ $rc -eq 139 ] && exit $rc
 for i in 1 2; do
   for S in 1 0; do
-    MTTS_PARITY_FF1_SPLIT=$S timeout -k 10 300 python bench.py --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_split$S.$i.json 2>/dev/null || exit $?
+    MTTS_PARITY_FF1_SPLIT=$S timeout -k 10 300 python bench.py --full --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_split$S.$i.json 2>/dev/null || exit $?
     echo "ff1_split=$S run $i: $(python -c "import json; d=json.loads([l for l in open('$O/ab_split$S.$i.json') if l.startswith('{')][-1]); print(d['ms_per_step'], d['precision_check']['modes']['parity_policy'])")"
   done
 done

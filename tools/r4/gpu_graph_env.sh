@@ -3,7 +3,7 @@
 # packet submission)?  Bench A/B of the HIP runtime's graph submission knobs -> gpurun_out/$TAG
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${TAG:-r4g}; mkdir -p $O; cd $R
 one() {  # $1 label, env set by caller
-  timeout -k 10 300 python bench.py --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_$1.json 2>/dev/null || return 1
+  timeout -k 10 300 python bench.py --full --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_$1.json 2>/dev/null || return 1
   echo "$1: $(python -c "import json; d=json.loads([l for l in open('$O/ab_$1.json') if l.startswith('{')][-1]); print(d['ms_per_step'])")"
 }
 for i in 1 2; do

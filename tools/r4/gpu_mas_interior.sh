@@ -11,5 +11,5 @@ for TR in auto 0 1; do
   echo "TR=$TR"; cat $O/mas_$TR.jsonl $O/prior_$TR.jsonl
 done
 unset MTTS_MAS_TR
-timeout -k 10 300 python bench.py --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/bench.json 2>/dev/null || exit $?
+timeout -k 10 300 python bench.py --full --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/bench.json 2>/dev/null || exit $?
 python tools/r4/bench_summary.py $O/bench.json | head -3

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${TAG:-r4c}; mkdir -p $O; cd $R
 TAG=${TAG:-r4c} bash tools/r4/gpu_suite.sh || exit $?
 for i in 1 2; do
   for F in 0 1; do
-    MTTS_GEMM_WS_PICK=$F timeout -k 10 200 python bench.py --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_ws$F.$i.json 2>/dev/null || exit $?
+    MTTS_GEMM_WS_PICK=$F timeout -k 10 200 python bench.py --full --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_ws$F.$i.json 2>/dev/null || exit $?
     echo "ws_pick=$F run $i: $(python -c "import json; d=json.loads([l for l in open('$O/ab_ws$F.$i.json') if l.startswith('{')][-1]); print(d['ms_per_step'])")"
   done
 done

@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest tests/test_training_gpu.py tests/test_head
 tail -1 $O/tests.log
 for i in 1 2; do
   for J in mas decoder; do
-    MTTS_PREFETCH_JOIN=$J timeout -k 10 300 python bench.py --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_$J.$i.json 2>/dev/null || exit $?
+    MTTS_PREFETCH_JOIN=$J timeout -k 10 300 python bench.py --full --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_$J.$i.json 2>/dev/null || exit $?
     echo "join=$J run $i: $(python -c "import json; d=json.loads([l for l in open('$O/ab_$J.$i.json') if l.startswith('{')][-1]); print(d['ms_per_step'], d['precision_check']['modes']['parity_policy'], d['maximum_path']['fused_prior_maximum_path_ms'])")"
   done
 done

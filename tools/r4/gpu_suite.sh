@@ -11,7 +11,7 @@ if [ "${SMOKE:-1}" = 1 ]; then
   tail -1 $O/smoke.log; [ $rc -ne 0 ] && { tail -20 $O/smoke.log; exit $rc; }
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 700 python bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err; rc=$?
+  timeout -k 10 700 python bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err; rc=$?
   echo "bench rc=$rc"; [ $rc -ne 0 ] && { tail -20 $O/bench.err; exit $rc; }
   python tools/r4/bench_summary.py $O/bench.json
 fi

@@ -8,7 +8,7 @@ tail -2 $O/tests.log; [ $rc -ne 0 ] && { grep -E "^FAILED|^E  .{0,200}|bf16-pari
 grep -E "rel err" $O/tests.log | head -20
 for i in 1 2; do
   for E in fp32fwd bf16x6; do
-    MTTS_PARITY_ENCODER=$E timeout -k 10 200 python bench.py --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_$E.$i.json 2>/dev/null || exit $?
+    MTTS_PARITY_ENCODER=$E timeout -k 10 200 python bench.py --full --no-extra --no-graph-profile --no-synth --no-cpu-baseline --steps 30 > $O/ab_$E.$i.json 2>/dev/null || exit $?
     echo "encoder=$E run $i: $(python -c "import json; d=json.loads([l for l in open('$O/ab_$E.$i.json') if l.startswith('{')][-1]); print(d['ms_per_step'], d['precision_check']['modes']['parity_policy'])")"
   done
 done

@@ -12,7 +12,7 @@ for rep in 1 2; do
     case $v in
       plain) E="" ;; dp) E="MTTS_FORCE_DP=1" ;; dpsplit) E="MTTS_FORCE_DP=1 MTTS_DP_SPLIT_OPT=1" ;;
     esac
-    env $E timeout -k 10 300 python bench.py $A > $O/$v$rep.json 2> $O/$v$rep.err || { echo "$v failed"; tail -5 $O/$v$rep.err; exit 1; }
+    env $E timeout -k 10 300 python bench.py --full $A > $O/$v$rep.json 2> $O/$v$rep.err || { echo "$v failed"; tail -5 $O/$v$rep.err; exit 1; }
     python -c "import json,sys; d=json.loads(open('$O/$v$rep.json').read().strip().splitlines()[-1]); print('$v', $rep, d['ms_per_step'])" >> $O/ab.txt
   done
 done

@@ -13,7 +13,7 @@ timeout -k 10 120 python3 -u tools/r6/glds_timeline.py --match 9600,256,768,3,79
 python3 -c "import json; d=json.load(open('$O/tl_9600_79.json')); print('timeline (tail on)', {k: d[k] for k in ('kernel_us','wave_life_us_mean','waves','start_quantiles_us')})"
 for i in 1 2; do
   for t in 0 1; do
-    MTTS_GEMM_TAIL=$t timeout -k 10 300 python bench.py --no-cpu-baseline --no-synth --no-extra --no-graph-profile --steps 30 > $O/bench_tail$t.$i.json 2> $O/bench_tail$t.$i.err || { echo "bench rc=$?"; tail -5 $O/bench_tail$t.$i.err; exit 1; }
+    MTTS_GEMM_TAIL=$t timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-synth --no-extra --no-graph-profile --steps 30 > $O/bench_tail$t.$i.json 2> $O/bench_tail$t.$i.err || { echo "bench rc=$?"; tail -5 $O/bench_tail$t.$i.err; exit 1; }
     python -c "import json,sys; s=open(sys.argv[1]).read(); d=json.loads(s[s.index('{'):]); print(sys.argv[1].split('/')[-1], d['ms_per_step'], d['precision_check']['bf16_loss_rel_err'], d['roofline']['avg_launch_us'])" $O/bench_tail$t.$i.json
   done
 done

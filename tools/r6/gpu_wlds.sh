@@ -9,7 +9,7 @@ timeout -k 10 400 python -u tools/r5/gemm_replay.py profiles/r05/gemm_log_parity
 tail -5 $O/replay.log; [ $rc -ne 0 ] && exit $rc
 for i in 1 2; do
   for pick in 0 1; do
-    MTTS_GEMM_WLDS_PICK=$pick timeout -k 10 300 python bench.py --no-cpu-baseline --no-synth --no-extra --no-graph-profile --steps 30 > $O/bench_pick$pick.$i.json 2> $O/bench_pick$pick.$i.err || { echo "bench rc=$?"; tail -5 $O/bench_pick$pick.$i.err; exit 1; }
+    MTTS_GEMM_WLDS_PICK=$pick timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-synth --no-extra --no-graph-profile --steps 30 > $O/bench_pick$pick.$i.json 2> $O/bench_pick$pick.$i.err || { echo "bench rc=$?"; tail -5 $O/bench_pick$pick.$i.err; exit 1; }
     python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[1].split('/')[-1], d['ms_per_step'], d['precision_check']['bf16_loss_rel_err'])" $O/bench_pick$pick.$i.json
   done
 done
