@@ -497,10 +497,6 @@ struct WgradGeom {
 // its tap-j A row m + off_j, so the per-step address advance is one uniform offset (rb * ld) and only
 // the tap validity needs the row's position u in its sequence (~12 instead of ~22 vector instructions
 // per staged row; the bias column sums only in the k-tile-0 blocks, behind a block-uniform branch).
-// HV = 2: two 4-wave halves per workgroup reduce the two halves of the split's row range into the same
-// 128 x 128 tile (own LDS rings, one shared barrier sequence: both halves run the same step count, rows
-// past their range masked), then add (half 0 + half 1, fixed order) before ONE slab write: the same waves
-// per CU as twice the workgroups, half the partial slabs that the step's batched reduce re-reads.
 // Batched launch: up to kWgradBatch independent weight gradients of the same kernel instantiation in one
 // grid (the blocks of job j are [first[j], first[j+1]); each job keeps its own row split, so a job's
 // partial slabs are bitwise those of its own launch).  The backward's queued weight gradients run this
@@ -510,71 +506,9 @@ struct WgradJobK {
     float *part, *part_db;  // the job's slabs [splits][N][K] and bias partials [splits][N] (or null)
     int32_t rps;            // token rows per split
     int32_t splits;
-    // in-kernel split sum (cnt != null): per-tile arrival counters (zero at rest) and where the sums go --
-    // dW[n*sn + c*sc + j*sj] for reduction column k = j*cin + c, db[n] -- (+=) when accumulate
-    int32_t *cnt;
-    float *dw, *db;
-    int64_t sn, sc, sj;
-    int32_t accumulate;
-    int32_t pad_;
 };
 
-// The last block of a tile to arrive sums the tile's split slabs in split order and writes dW (and db):
-// every block's slab stores are published by an agent-scope release before its ticket (fetch_add on the
-// tile's counter); the last arriver acquires, reads every slab with plain vector loads, and re-zeroes the
-// counter.  The sum order is fixed (split 0, 1, ...) whatever the arrival order: deterministic, and no
-// separate reduce launch or its re-read of the slabs from HBM.
-__device__ __forceinline__ void wgrad_combine(const WgradJobK &J, int tile, int n0, int k0, bool ktile0) {
-    __shared__ int s_last;
-    const mtts_conv_wgrad_args &p = J.a;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's slab / db stores have completed
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int old = __hip_atomic_fetch_add(J.cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == J.splits - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;  // block-uniform
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const size_t NK = (size_t)p.N * p.K;
-    const int nthr = (int)blockDim.x;
-    // 128 x 128 tile as float4 groups along k (K = ntaps * cin, cin % 8 == 0: a group is all in or out)
-    for (int g = (int)threadIdx.x; g < 128 * 32; g += nthr) {
-        const int n = n0 + (g >> 5), k = k0 + (g & 31) * 4;
-        if (n >= p.N || k >= p.K) continue;
-        const float *src = J.part + (size_t)n * p.K + k;
-        float4 a = *reinterpret_cast<const float4 *>(src);
-        for (int sp = 1; sp < J.splits; ++sp) {
-            const float4 b = *reinterpret_cast<const float4 *>(src + sp * NK);
-            a.x += b.x;
-            a.y += b.y;
-            a.z += b.z;
-            a.w += b.w;
-        }
-        const float v[4] = {a.x, a.y, a.z, a.w};
-        const int j0 = k / p.cin, c0 = k - j0 * p.cin;  // the group lies inside one tap (cin % 4 == 0)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float *o = J.dw + n * J.sn + (int64_t)(c0 + e) * J.sc + (int64_t)j0 * J.sj;
-            *o = J.accumulate ? *o + v[e] : v[e];
-        }
-    }
-    if (ktile0 && J.part_db && J.db) {
-        for (int x = (int)threadIdx.x; x < 128; x += nthr) {
-            const int n = n0 + x;
-            if (n >= p.N) continue;
-            float a = J.part_db[n];
-            for (int sp = 1; sp < J.splits; ++sp) a += J.part_db[(size_t)sp * p.N + n];
-            J.db[n] = J.accumulate ? J.db[n] + a : a;
-        }
-    }
-    if (threadIdx.x == 0) __hip_atomic_store(J.cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-constexpr int kWgradBatch = 12;  // ~1.7 KiB of kernel arguments
+constexpr int kWgradBatch = 12;
 struct WgradBatch {
     WgradJobK job[kWgradBatch];
     int32_t first[kWgradBatch + 1];
@@ -582,7 +516,7 @@ struct WgradBatch {
 };
 
 // One (tile, split) block of a batch: vb is its index in the batch's block numbering.
-template <bool BF16, int KB, int DEPTH, bool INC, bool ABF16, bool YBF16, bool LIN, int HV>
+template <bool BF16, int KB, int DEPTH, bool INC, bool ABF16, bool YBF16, bool LIN>
 __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) {
     int jb = 0;  // this block's job (block-uniform scan over the batch's first-block table)
     while (jb + 1 < wb.njobs && vb >= wb.first[jb + 1]) ++jb;
@@ -591,9 +525,6 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
     float *__restrict__ part = wb.job[jb].part;
     float *__restrict__ part_db = wb.job[jb].part_db;
     const int blk = vb - wb.first[jb], nblk = wb.first[jb + 1] - wb.first[jb];
-    static_assert(HV == 1 || (HV == 2 && DEPTH == 1), "two halves: one step in flight");
-    static_assert(HV == 1 || (size_t)64 * kThreads * sizeof(float) <= 2 * WgradGeom<BF16, KB>::kLds,
-                  "half 1's accumulators fit the two halves' LDS");
     static_assert(!ABF16 || BF16, "bf16 A needs the bf16 path");
     static_assert(!YBF16 || BF16, "bf16 dY needs the bf16 path");
     static_assert(!LIN || INC, "the linear row walk is a special case of the incremental one");
@@ -603,11 +534,10 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
     using ST = typename Gm::ST;
     constexpr int T = Gm::T, LDR = Gm::LDR, LDW = Gm::LDW, IMG = Gm::kImg, CH = Gm::CH;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int hv = HV == 2 ? (int)(threadIdx.x >> 8) : 0;  // this thread's half
-    ST *Ybuf = reinterpret_cast<ST *>(smem) + hv * 4 * IMG;  // per half: [2][IMG] then Xs [2][IMG]
+    ST *Ybuf = reinterpret_cast<ST *>(smem);  // [2][IMG] then Xs [2][IMG]
     ST *Xbuf = Ybuf + 2 * IMG;
 
-    const int tid = (int)threadIdx.x & (kThreads - 1), lane = tid & 63, wave = tid >> 6;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int lr = lane & 31, lh = lane >> 5;
     // 1-D grid relabelled XCD-contiguous (as conv_gemm_kernel), tiles numbered n-fastest, then k, then
@@ -625,10 +555,8 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
         k0 = ktile * T;
     }
     const int M = p.nb * p.To;
-    // HV = 2: rows_per_split is a multiple of 2 KB; half h takes [split start + h * rows / 2, + rows / 2)
-    const int h_rows = rows_per_split / HV;
-    const int r_begin = split * rows_per_split + hv * h_rows;
-    const int r_end = min(M, r_begin + h_rows);
+    const int r_begin = split * rows_per_split;
+    const int r_end = min(M, r_begin + rows_per_split);
     const bool do_db = (ktile == 0) && part_db != nullptr;
     const float inv_to = 1.0f / (float)p.To;
 
@@ -882,40 +810,7 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
         }
     };
 
-    if constexpr (HV == 2) {
-        // both halves: the same step count (block-wide barriers), rows past r_end masked by load()
-        load(R0, r_begin);
-        int buf = 0;
-        for (int s = 0; s < h_rows / KB; ++s) {
-            const int rb = r_begin + s * KB;
-            store(R0, buf);
-            mtts::lds_barrier();
-            load(R0, rb + KB);
-            if (g_pin_prefetch) __builtin_amdgcn_sched_barrier(0);
-            compute(buf);
-            buf ^= 1;
-        }
-        // half 1's accumulators -> LDS (lane-fastest: conflict-free), half 0 adds them: acc0 + acc1
-        float *xs = reinterpret_cast<float *>(smem);
-        __syncthreads();
-        if (hv == 1) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) xs[((i * 2 + j) * 16 + v) * kThreads + tid] = acc[i][j][v];
-        }
-        __syncthreads();
-        if (hv == 0) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) acc[i][j][v] += xs[((i * 2 + j) * 16 + v) * kThreads + tid];
-        }
-    } else if (r_begin < r_end) {
+    if (r_begin < r_end) {
         if constexpr (DEPTH == 2) {
             load(R0, r_begin);
             load(R1, r_begin + KB);
@@ -950,7 +845,7 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
 
     float *slab = part + (size_t)split * p.N * p.K;
 #pragma unroll
-    for (int i = 0; i < 2 && hv == 0; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int k = k0 + wc * 64 + j * 32 + lr;
@@ -964,34 +859,30 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
     if (do_db) {
         // (row pair, column) partial sums -> LDS scratch (reusing the operand buffers), then a fixed-order
         // sum over the KB/2 row pairs (deterministic, no float atomics)
-        float *dbs = reinterpret_cast<float *>(smem);  // [HV][KB/2][T]
+        float *dbs = reinterpret_cast<float *>(smem);  // [KB/2][T]
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < CH; ++c)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dbs[(hv * (KB / 2) + c_rp[c]) * T + c_cc[c] + i] = colsum[c][i];
+            for (int i = 0; i < 4; ++i) dbs[c_rp[c] * T + c_cc[c] + i] = colsum[c][i];
         __syncthreads();
-        for (int x = (int)threadIdx.x; x < T; x += kThreads * HV) {
+        for (int x = (int)threadIdx.x; x < T; x += kThreads) {
             const int n = n0 + x;
             float sacc = 0.f;
-            for (int g = 0; g < HV * (KB / 2); ++g) sacc += dbs[g * T + x];
+            for (int g = 0; g < KB / 2; ++g) sacc += dbs[g * T + x];
             if (n < p.N) part_db[(size_t)split * p.N + n] = sacc;
         }
-    }
-    if (wb.job[jb].cnt) {
-        const int ntn = (p.N + T - 1) / T;
-        wgrad_combine(wb.job[jb], ktile * ntn + n0 / T, n0, k0, ktile == 0);
     }
 }
 
 // The batch's blocks on gridDim.x workgroups: one each when the grid covers them (the default), else a
 // workgroup walks several (a capped grid leaves CUs to a concurrent stream: the side-stream flush, see
 // mtts_wgrad_flush_cap).  Whole-block-uniform loop; the barrier protects the LDS images between blocks.
-template <bool BF16, int KB, int DEPTH, bool INC, bool ABF16 = false, bool YBF16 = false, bool LIN = false, int HV = 1>
-__global__ __launch_bounds__(kThreads * HV) void conv_wgrad_kernel(const WgradBatch wb) {
+template <bool BF16, int KB, int DEPTH, bool INC, bool ABF16 = false, bool YBF16 = false, bool LIN = false>
+__global__ __launch_bounds__(kThreads) void conv_wgrad_kernel(const WgradBatch wb) {
     const int total = wb.first[wb.njobs];
     for (int vb = (int)blockIdx.x; vb < total; vb += (int)gridDim.x) {
-        wgrad_block<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN, HV>(wb, vb);
+        wgrad_block<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN>(wb, vb);
         __syncthreads();
     }
 }
@@ -1440,41 +1331,40 @@ extern "C" int mtts_act_dropout_bwd_scaled(const float *dy, const float *y, cons
 
 // Split of the token rows over blocks: about target_blocks blocks in total, whole KB-row steps.
 constexpr int kWgradMaxTarget = 1024;
+// More blocks keep more row steps in flight per CU (the kernel is latency-bound) but every split adds
+// an N x K fp32 slab that the step's batched reduce reads back.  In-kernel, bf16-stored operands liked
+// ~3 blocks per CU (19200-row conv 49.8 -> 38.4 us, tools/wgrad_store_ab.py), but the whole step --
+// wgrad + its slab reduce -- is fastest at ~2 blocks per CU for bf16 operands and ~1.5 for fp32 ones
+// (same-box step sweep, tools/gpu_ab3.sh: 768/256 8.585 ms, 512/256 8.505, 512/384 8.47, 512/512 8.63,
+// 256/256 8.65; profiles/r02/step_ab_round2b.txt)
+constexpr int kWgradMinBlocks = 384;    // fp32 operands
+constexpr int kWgradMinBlocks16 = 512;  // a bf16 A or dY
+constexpr int kWgradSplitRows = 768;
+// round 5, with the prefetch fence: 64 minimum blocks per batched job (same box, three alternating rounds:
+// 7.410 / 7.409 / 7.383 vs 7.457 / 7.452 / 7.455 ms at 128; profiles/r05/ab/wgrad_min_blocks_ab.txt) -- the
+// side-stream batch crowds the encoder's backward less
+constexpr int kWgradBatchedMinBlocks = 64;
+// round 5: 3072 rows per split in the batched launches (same-box step A/B: 7.604 / 7.583 vs 7.611 / 7.631 ms
+// at 1536; 1024 and 4608 slower; profiles/r05/wgrad_split_ab.txt) -- fewer slabs to sum
+constexpr int kWgradBatchedSplitRows = 3072;
+constexpr int kWgradMinSteps = 4;  // at least this many row steps per split
+constexpr int kWgradDefaultKB = 32;  // rows per step where the caller does not choose (64: bf16 only)
 // target_blocks < 0: the sweep's rule (tools/wgrad_sweep.py) -- about 768 rows per split (long enough
-// to amortize the pipeline and the split's slab write) but never fewer than min_blocks (below).
+// to amortize the pipeline and the split's slab write) but never fewer than the minimum block count.
 // batched: the job is queued for a batched launch (mtts::flush_wgrads) whose other jobs fill the chip
 // beside it, so it takes fewer, longer splits -- fewer N x K slabs to write and sum (step sweep with the
 // whole backward's weight gradients batched at its end, same box: min blocks 384/512 + 768 rows 7.62 ms,
 // 256/256 7.41, 128/128 + 768 rows 7.36, 128/128 + 1536 rows 7.34, 64/64 + 3072 rows 7.58).
 static void wgrad_plan(const mtts_conv_wgrad_args &p, int kb, int target_blocks, int *splits, int *rows_per_split,
-                       int hv = 1, bool batched = false) {
+                       bool batched = false) {
     const int M = p.nb * p.To;
     const int tiles = ((p.N + 127) / 128) * ((p.K + 127) / 128);
-    // More blocks keep more row steps in flight per CU (the kernel is latency-bound) but every split adds
-    // an N x K fp32 slab that the step's batched reduce reads back.  In-kernel, bf16-stored operands liked
-    // ~3 blocks per CU (19200-row conv 49.8 -> 38.4 us, tools/wgrad_store_ab.py), but the whole step --
-    // wgrad + its slab reduce -- is fastest at ~2 blocks per CU for bf16 operands and ~1.5 for fp32 ones
-    // (same-box step sweep, tools/gpu_ab3.sh: 768/256 8.585 ms, 512/256 8.505, 512/384 8.47, 512/512 8.63,
-    // 256/256 8.65; profiles/r02/step_ab_round2b.txt)
-    static const int min_blocks = [] { const char *e = getenv("MTTS_WGRAD_MINBLK"); return e ? atoi(e) : 384; }();
-    static const int min_blocks16 = [] { const char *e = getenv("MTTS_WGRAD_MINBLK16"); return e ? atoi(e) : 512; }();
-    static const int split_rows = [] { const char *e = getenv("MTTS_WGRAD_ROWS"); return e && atoi(e) > 0 ? atoi(e) : 768; }();
-    // round 5, with the prefetch fence: 64 minimum blocks per batched job (same box, three alternating rounds:
-    // 7.410 / 7.409 / 7.383 vs 7.457 / 7.452 / 7.455 ms at 128; profiles/r05/ab/wgrad_min_blocks_ab.txt) -- the
-    // side-stream batch crowds the encoder's backward less
-    static const int b_min_blocks = [] { const char *e = getenv("MTTS_WGRAD_BMINBLK"); return e ? atoi(e) : 64; }();
-    // round 5: 3072 rows per split in the batched launches (same-box step A/B, tools/r5/gpu_ab_wgrad.sh: 7.604 / 7.583
-    // vs 7.611 / 7.631 ms at 1536; 1024 and 4608 slower; profiles/r05/wgrad_split_ab.txt) -- fewer slabs to sum
-    static const int b_split_rows = [] { const char *e = getenv("MTTS_WGRAD_BROWS"); return e && atoi(e) > 0 ? atoi(e) : 3072; }();
-    // hv = 2: two-half workgroups (twice the waves each): half the workgroups, rows in whole double steps
-    const int mb = (batched ? b_min_blocks
-                            : (p.flags & (MTTS_GEMM_F_A_BF16 | MTTS_WGRAD_F_DY_BF16)) ? min_blocks16 : min_blocks) / hv;
-    const int rows = batched ? b_split_rows : split_rows;
-    kb *= hv;
+    const bool op16 = (p.flags & (MTTS_GEMM_F_A_BF16 | MTTS_WGRAD_F_DY_BF16)) != 0;
+    const int mb = batched ? kWgradBatchedMinBlocks : op16 ? kWgradMinBlocks16 : kWgradMinBlocks;
+    const int rows = batched ? kWgradBatchedSplitRows : kWgradSplitRows;
     int s = target_blocks > 0 ? (target_blocks + tiles - 1) / tiles
                               : max((mb + tiles - 1) / tiles, (M + rows / 2) / rows);
-    static const int min_steps = [] { const char *e = getenv("MTTS_WGRAD_MINSTEPS"); return e && atoi(e) > 0 ? atoi(e) : 4; }();
-    s = max(1, min(s, (M + min_steps * kb - 1) / (min_steps * kb)));  // at least min_steps steps per split
+    s = max(1, min(s, (M + kWgradMinSteps * kb - 1) / (kWgradMinSteps * kb)));
     int rps = (M + s - 1) / s;
     rps = (rps + kb - 1) / kb * kb;
     *rows_per_split = max(rps, kb);
@@ -1488,7 +1378,7 @@ extern "C" size_t mtts_conv_wgrad_workspace_size(const mtts_conv_wgrad_args *arg
     wgrad_plan(*args, 32, kWgradMaxTarget, &splits, &rps);
     wgrad_plan(*args, 32, -1, &s2, &r2);
     splits = max(splits, s2);
-    wgrad_plan(*args, 32, -1, &s2, &r2, 1, true);
+    wgrad_plan(*args, 32, -1, &s2, &r2, true);
     splits = max(splits, s2);
     return mtts::align_up((size_t)splits * args->N * args->K * 4, 256) + (size_t)splits * args->N * 4 + 256;
 }
@@ -1496,41 +1386,26 @@ extern "C" size_t mtts_conv_wgrad_workspace_size(const mtts_conv_wgrad_args *arg
 // mtts_wgrad_flush_cap: > 0 caps the grid of the batched weight-gradient launches (0: one workgroup per block)
 std::atomic<int> g_wgrad_cap{0};
 
-template <bool BF16, int KB, int DEPTH, bool INC, bool ABF16 = false, bool YBF16 = false, bool LIN = false, int HV = 1>
-static int wgrad_launch_hv(const WgradBatch &wb, hipStream_t st) {
+template <bool BF16, int KB, int DEPTH, bool INC, bool ABF16 = false, bool YBF16 = false, bool LIN = false>
+static int wgrad_launch_k(const WgradBatch &wb, hipStream_t st) {
     using Gm = WgradGeom<BF16, KB>;
-    constexpr size_t lds = Gm::kLds * HV;
+    constexpr size_t lds = Gm::kLds;
     static bool attr_set = false;
     if (lds > 64 * 1024 && !attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_kernel<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN, HV>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_kernel<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return mtts::fail(MTTS_ERR_HIP, "conv_wgrad: LDS attribute");
         attr_set = true;
     }
     const int total = wb.first[wb.njobs], cap = g_wgrad_cap.load();
-    hipLaunchKernelGGL((conv_wgrad_kernel<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN, HV>),
-                       dim3((unsigned)(cap > 0 && cap < total ? cap : total)), dim3(kThreads * HV), lds, st, wb);
+    hipLaunchKernelGGL((conv_wgrad_kernel<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN>),
+                       dim3((unsigned)(cap > 0 && cap < total ? cap : total)), dim3(kThreads), lds, st, wb);
     return mtts::check_launch("conv_wgrad_kernel");
-}
-
-// MTTS_WGRAD_HV=2: the two-half workgroups for the KB = 32, one-step schedules (see conv_wgrad_kernel)
-static int wgrad_hv() {
-    static const int hv = [] { const char *e = getenv("MTTS_WGRAD_HV"); return e && atoi(e) == 2 ? 2 : 1; }();
-    return hv;
-}
-
-template <bool BF16, int KB, int DEPTH, bool INC, bool ABF16 = false, bool YBF16 = false, bool LIN = false>
-static int wgrad_launch_k(const WgradBatch &wb, bool hv2, hipStream_t st) {
-    if constexpr (KB == 32 && DEPTH == 1) {
-        if (hv2) return wgrad_launch_hv<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN, 2>(wb, st);
-    }
-    return wgrad_launch_hv<BF16, KB, DEPTH, INC, ABF16, YBF16, LIN, 1>(wb, st);
 }
 
 // The linear row walk (LIN): every row's dY / A rows follow from the token row index alone.
 static bool wgrad_lin_ok(const mtts_conv_wgrad_args &p) {
-    static const bool off = [] { const char *e = getenv("MTTS_WGRAD_LIN"); return e && e[0] == '0'; }();
-    return !off && p.in_stride == 1 && p.out_stride == 1 && p.out_off == 0 && p.To_full == p.To && p.Ti == p.To;
+    return p.in_stride == 1 && p.out_stride == 1 && p.out_off == 0 && p.To_full == p.To && p.Ti == p.To;
 }
 
 // The incremental row walk needs one wrap per step (To >= KB) and element offsets that stay inside
@@ -1545,15 +1420,15 @@ static bool wgrad_inc_ok(const mtts_conv_wgrad_args &p, int kb) {
 // Everything the instantiation choice below depends on: jobs with equal keys run the same kernel and can
 // share one batched launch.
 struct WgradKey {
-    bool bf16, a16, y16, inc, lin, hv2;
+    bool bf16, a16, y16, inc, lin;
     int kb, depth;
     bool operator==(const WgradKey &o) const {
-        return bf16 == o.bf16 && a16 == o.a16 && y16 == o.y16 && inc == o.inc && lin == o.lin && hv2 == o.hv2 &&
-               kb == o.kb && depth == o.depth;
+        return bf16 == o.bf16 && a16 == o.a16 && y16 == o.y16 && inc == o.inc && lin == o.lin && kb == o.kb &&
+               depth == o.depth;
     }
 };
 
-static WgradKey wgrad_key(const mtts_conv_wgrad_args &p, bool bf16, int kb, int depth, int rps) {
+static WgradKey wgrad_key(const mtts_conv_wgrad_args &p, bool bf16, int kb, int depth) {
     WgradKey k;
     k.bf16 = bf16;
     k.kb = bf16 ? kb : 32;
@@ -1562,8 +1437,6 @@ static WgradKey wgrad_key(const mtts_conv_wgrad_args &p, bool bf16, int kb, int 
     k.y16 = (p.flags & MTTS_WGRAD_F_DY_BF16) != 0;
     k.inc = wgrad_inc_ok(p, k.kb);
     k.lin = k.bf16 && k.kb == 32 && k.depth == 1 && k.inc && k.a16 && !k.y16 && wgrad_lin_ok(p);
-    // (any split of whole double steps is exact with two halves; the plan makes them so when hv = 2)
-    k.hv2 = k.kb == 32 && k.depth == 1 && wgrad_hv() == 2 && rps % (2 * k.kb) == 0;
     return k;
 }
 
@@ -1573,19 +1446,19 @@ static int wgrad_launch(const WgradBatch &wb, const WgradKey &k, hipStream_t st)
         // the linear walk measured faster only with a bf16 A and an fp32 dY (19200-row conv: 44.4 vs 48.0 us;
         // fp32 / fp32 42.7 vs 42.9, bf16 dY 48.1 vs 42.9: tools/wgrad_store_ab.py) -- the staging's VALU is
         // not what bounds the other storages
-        if (KB == 32 && k.lin) return wgrad_launch_k<true, 32, 1, true, true, false, true>(wb, k.hv2, st);
+        if (KB == 32 && k.lin) return wgrad_launch_k<true, 32, 1, true, true, false, true>(wb, st);
         if (k.a16 && k.y16)
-            return k.inc ? wgrad_launch_k<true, KB, 1, true, true, true>(wb, k.hv2, st)
-                         : wgrad_launch_k<true, KB, 1, false, true, true>(wb, k.hv2, st);
+            return k.inc ? wgrad_launch_k<true, KB, 1, true, true, true>(wb, st)
+                         : wgrad_launch_k<true, KB, 1, false, true, true>(wb, st);
         if (k.y16)
-            return k.inc ? wgrad_launch_k<true, KB, 1, true, false, true>(wb, k.hv2, st)
-                         : wgrad_launch_k<true, KB, 1, false, false, true>(wb, k.hv2, st);
+            return k.inc ? wgrad_launch_k<true, KB, 1, true, false, true>(wb, st)
+                         : wgrad_launch_k<true, KB, 1, false, false, true>(wb, st);
         if (k.a16)
-            return k.inc ? wgrad_launch_k<true, KB, 1, true, true>(wb, k.hv2, st)
-                         : wgrad_launch_k<true, KB, 1, false, true>(wb, k.hv2, st);
+            return k.inc ? wgrad_launch_k<true, KB, 1, true, true>(wb, st)
+                         : wgrad_launch_k<true, KB, 1, false, true>(wb, st);
     }
-    return k.inc ? wgrad_launch_k<BF16, KB, DEPTH, true>(wb, k.hv2, st)
-                 : wgrad_launch_k<BF16, KB, DEPTH, false>(wb, k.hv2, st);
+    return k.inc ? wgrad_launch_k<BF16, KB, DEPTH, true>(wb, st)
+                 : wgrad_launch_k<BF16, KB, DEPTH, false>(wb, st);
 }
 
 static int wgrad_launch_key(const WgradBatch &wb, const WgradKey &k, hipStream_t st) {
@@ -1637,52 +1510,10 @@ static int wgrad_blocks(const WgradPlanned &w) {
     return ((p.N + 127) / 128) * ((p.K + 127) / 128) * w.splits;
 }
 
-// Deferred weight gradients (between mtts_defer_reductions(1) and the next flush, MTTS_DEFER_WGRAD != 0):
+// Deferred weight gradients (between mtts_defer_reductions(1) and the next flush):
 // queued here and launched batched by mtts::flush_wgrads, which mtts_flush_reductions calls first.
 std::mutex g_wq_mu;
 std::vector<WgradPlanned> g_wq;
-
-static bool defer_wgrads() {
-    static const bool on = [] { const char *e = getenv("MTTS_DEFER_WGRAD"); return !(e && e[0] == '0'); }();
-    return on && mtts::deferring();
-}
-
-// Arrival counters of the in-kernel split sums (wgrad_combine): one zeroed pool per device, handed out as a
-// ring (each launch's tiles get their own counters; the last arriver of a tile re-zeroes its counter, so a
-// range is free again once its launch has run).  Opt-in, MTTS_WGRAD_FUSED_SUM=1: measured in the graph-replayed
-// step (round 4, profiles/r04/fused_wgrad_sum/) the weight-gradient family took 4.2 ms instead of 1.2 + 0.29 ms
-// (GEMMs + the batched reduce launches): every block's agent-scope release writes back its XCD's dirty L2
-// lines (a 64 KB slab per block, ~6.5 us per 16 KB in MI355X_MICROARCH.md's price list) before its ticket, on
-// the block's own critical path.  Default: the separate fixed-order reduce launch.
-constexpr int kCntPool = 1 << 16;
-// (A fence-free variant -- whole-line slab stores, the last arriver polling the counter with sc1 loads -- gave
-// wrong sums and a poll that never matched (the counter line stale in the reader's L2): removed, round 4.)
-static int32_t *wgrad_counters(int n, hipStream_t st) {
-    static const bool off = [] { const char *e = getenv("MTTS_WGRAD_FUSED_SUM"); return !(e && e[0] == '1'); }();
-    if (off || n <= 0 || n > kCntPool / 16) return nullptr;
-    static std::mutex mu;
-    static int32_t *pool[64] = {};
-    static int head[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!pool[dev]) {
-        // never allocated inside a stream capture (the caller then takes the separate reduce launch)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
-        int32_t *p = nullptr;
-        if (hipMalloc(&p, kCntPool * sizeof(int32_t)) != hipSuccess) return nullptr;
-        if (hipMemset(p, 0, kCntPool * sizeof(int32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-            (void)hipFree(p);
-            return nullptr;
-        }
-        pool[dev] = p;
-    }
-    if (head[dev] + n > kCntPool) head[dev] = 0;
-    int32_t *r = pool[dev] + head[dev];
-    head[dev] += (n + 15) / 16 * 16;
-    return r;
-}
 
 // mtts_wgrad_plan_mode: 0 = the batched split plan for queued gradients, the per-launch one otherwise;
 // 1 / 2 = always the batched / per-launch plan (tests: a queued and an immediate gradient bitwise equal)
@@ -1702,9 +1533,7 @@ static int conv_wgrad_impl(const mtts_conv_wgrad_args *args, int32_t precision, 
     MTTS_CHECK_ARG(p.ldy % 4 == 0 && (uintptr_t)p.dY % 16 == 0, "conv_wgrad: dY rows must be 16-byte aligned");
     MTTS_CHECK_ARG(precision == MTTS_PREC_BF16 || precision == MTTS_PREC_FP32, "conv_wgrad: bad precision");
     const bool bf16 = precision == MTTS_PREC_BF16;
-    // MTTS_WGRAD_KB=64: 64-row steps by default in bf16 (A/B switch)
-    static const int default_kb = [] { const char *e = getenv("MTTS_WGRAD_KB"); return e && atoi(e) == 64 ? 64 : 32; }();
-    if (rows_per_step < 0) rows_per_step = bf16 ? default_kb : 32;
+    if (rows_per_step < 0) rows_per_step = kWgradDefaultKB;
     if (depth < 0) depth = 1;
     if (p.flags & (MTTS_GEMM_F_A_BF16 | MTTS_WGRAD_F_DY_BF16)) {
         MTTS_CHECK_ARG(bf16 && depth == 1 && p.lda % 4 == 0 && (uintptr_t)p.A % 8 == 0,
@@ -1718,11 +1547,9 @@ static int conv_wgrad_impl(const mtts_conv_wgrad_args *args, int32_t precision, 
         return mtts::fail(MTTS_ERR_WORKSPACE, "conv_wgrad: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     int splits, rps;
-    // the two-half workgroups serve the register-staged KB = 32, one-step schedules
-    const int hv = (wgrad_hv() == 2 && rows_per_step == 32 && depth == 1) ? 2 : 1;
-    const bool queue = p.nb * p.To > 0 && defer_wgrads();
+    const bool queue = p.nb * p.To > 0 && mtts::deferring();
     const int pm = g_wgrad_plan_mode.load();
-    wgrad_plan(p, rows_per_step, target_blocks, &splits, &rps, hv, pm == 1 || (pm == 0 && queue));
+    wgrad_plan(p, rows_per_step, target_blocks, &splits, &rps, pm == 1 || (pm == 0 && queue));
     WgradPlanned w;
     w.k.a = p;
     w.k.part = static_cast<float *>(workspace);
@@ -1731,15 +1558,7 @@ static int conv_wgrad_impl(const mtts_conv_wgrad_args *args, int32_t precision, 
                      : nullptr;
     w.k.rps = rps;
     w.k.splits = splits;
-    w.k.cnt = nullptr;
-    w.k.dw = dw;
-    w.k.db = db;
-    w.k.sn = sn;
-    w.k.sc = sc;
-    w.k.sj = sj;
-    w.k.accumulate = accumulate;
-    w.k.pad_ = 0;
-    w.key = wgrad_key(p, bf16, rows_per_step, depth, rps);
+    w.key = wgrad_key(p, bf16, rows_per_step, depth);
     w.splits = splits;
     w.dw = dw;
     w.sn = sn;
@@ -1757,8 +1576,6 @@ static int conv_wgrad_impl(const mtts_conv_wgrad_args *args, int32_t precision, 
         w.splits = 1;
         w.k.part_db = db ? part_db : nullptr;
     } else {
-        // in-kernel split sums (no reduce job) when enabled and the counter pool is available
-        w.k.cnt = wgrad_counters(((p.N + 127) / 128) * ((p.K + 127) / 128), st);
         if (queue) {
             std::lock_guard<std::mutex> lk(g_wq_mu);
             g_wq.push_back(w);
@@ -1770,7 +1587,6 @@ static int conv_wgrad_impl(const mtts_conv_wgrad_args *args, int32_t precision, 
         wb.first[1] = wgrad_blocks(w);
         wb.njobs = 1;
         if ((rc = wgrad_launch_key(wb, w.key, st))) return rc;
-        if (w.k.cnt) return MTTS_OK;
     }
     // sum of the split slabs (reduce.hip: now, or queued for the step's batched launch)
     mtts_reduce_job jobs[2];
@@ -1808,7 +1624,6 @@ int flush_wgrads(hipStream_t st) {
     }
     std::vector<mtts_reduce_job> jobs;
     for (const WgradPlanned &w : q) {
-        if (w.k.cnt) continue;  // summed in-kernel
         mtts_reduce_job j2[2];
         const int n = wgrad_reduce_jobs(w, j2);
         jobs.insert(jobs.end(), j2, j2 + n);

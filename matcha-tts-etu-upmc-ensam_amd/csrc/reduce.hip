@@ -17,7 +17,7 @@
 // Deferral (mtts_defer_reductions) queues the jobs of a whole backward pass and mtts_flush_reductions
 // runs them in one batched launch; the queue is process-wide because autograd calls the backward
 // entry points from its own thread.  The weight-gradient GEMMs themselves are deferred too
-// (conv_gemm.hip, MTTS_DEFER_WGRAD): a flush first launches them batched, then their slab sums.
+// (conv_gemm.hip): a flush first launches them batched, then their slab sums.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

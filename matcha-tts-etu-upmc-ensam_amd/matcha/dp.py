@@ -238,7 +238,7 @@ class GradBucketReducer:
             self.flat[self.n_grad:].copy_(self._pending_scalars)
 
     def _issue(self, k: int) -> None:
-        from matcha.models.components import _ops as OPS
+        from matcha.models.components import _defer as D
 
         lo, hi = self.spans[k]
         if self.watchdog is not None:
@@ -246,7 +246,7 @@ class GradBucketReducer:
         if self.overlap and self.stream is not None:
             # the bucket's weight gradients may still be queued: they run on the deferral's side stream
             # (joined at the deferral's exit); pack + all-reduce here wait for the main and the side stream
-            side = OPS.flush_for_bucket()
+            side = D.flush_for_bucket()
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             if side is not None:
                 self.stream.wait_stream(side)
@@ -261,7 +261,7 @@ class GradBucketReducer:
                 if self.progress is not None:
                     self.progress.mark_bucket(k, self.stream)
         else:
-            OPS.flush_deferred_grad_sums()  # on the current stream (joins the side stream first)
+            D.flush_deferred_grad_sums()  # on the current stream (joins the side stream first)
             self._pack(k)
             if self.overlap:  # CPU (gloo): eager, in order
                 self.comm.all_reduce_(self.flat[lo:hi])

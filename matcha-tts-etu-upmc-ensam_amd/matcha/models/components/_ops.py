@@ -31,6 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from matcha import _native as N
+from matcha.models.components._defer import _grad_sums, _keep_partials, keep_for_side, param_grad_side_stream
 
 PREC_FP32, PREC_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_RELU, ACT_DRELU = 0, 1, 2, 3, 4
@@ -625,253 +626,8 @@ def _gemm(A, Ti, To, nb, in_stride, offs, cin, Wp, Kp, N_, C, To_full, out_strid
                          bias=bias is not None, aux=aux is not None)))
 
 
-# Weight gradients off the critical path: inside side_stream_wgrad() every _wgrad launches on a
-# side stream (after the main stream's work so far), so a layer's wgrad + slab reduce overlap the
-# dgrad chain that the previous layer waits for -- the backward's kernels are latency-bound and leave
-# the chip under-filled one at a time.  Every tensor a side launch touches is kept alive until
-# join_side_streams() (the main stream then waits for the side stream), so the caching allocator
-# cannot hand its memory to the main stream early; and because that extra reference raises the
-# tensors' use count, autograd never accumulates into a pass-through gradient in place while the side
-# stream still reads it.  The outputs dw / db are NOT kept (AccumulateGrad then steals them without a
-# kernel); nothing on the main stream reads them before the join.  Only for steps where autograd does
-# not accumulate into existing .grad tensors (fresh gradients, one micro-batch): the Trainer's graph
-# step.
-_SIDE_WGRAD = {"on": False, "streams": {}, "keep": []}
-
-
-@contextlib.contextmanager
-def side_stream_wgrad(enabled: bool = True):
-    prev = _SIDE_WGRAD["on"]
-    _SIDE_WGRAD["on"] = enabled
-    try:
-        yield
-    finally:
-        _SIDE_WGRAD["on"] = prev
-        join_side_streams()
-
-
-def join_side_streams():
-    for dev, side in _SIDE_WGRAD["streams"].items():
-        torch.cuda.current_stream(dev).wait_stream(side)
-    _SIDE_WGRAD["keep"].clear()
-
-
-# Parameter-gradient sums deferred to one batched launch (csrc/reduce.hip): inside
-# deferred_grad_sums() the weight-gradient GEMMs and the norm backwards only QUEUE the fixed-order sums
-# of their partial slabs; the context exit runs the queue as one launch instead of ~120 small ones.
-# The weight-gradient GEMMs themselves are queued too (csrc/conv_gemm.hip, MTTS_DEFER_WGRAD=0 turns it
-# off) and a flush launches them batched -- up to 12 layers per launch, each job keeping its own row split,
-# so a job's slabs are bitwise those of its own launch with the same plan -- before their sums.  The plan
-# itself differs by default (mtts_wgrad_plan_mode(0)): a queued job takes the batched split plan (fewer,
-# longer splits), an immediate one the per-launch plan, so the two round differently (both deterministic);
-# mtts_wgrad_plan_mode(1) gives every job the batched plan (the tests that compare them bitwise set it).
-# The workspaces holding the partials (and the queued GEMMs' inputs) are kept alive until then.  Valid only while nothing reads a
-# parameter gradient before the exit: fresh gradients (AccumulateGrad steals them, no copy kernel) of
-# LEAF weights -- a Function whose weights are not all leaves (ctx.leaf False) sums at once.
-_DEFER = {"on": False, "seam": False, "keep": [], "side_keep": [], "side": {}, "side_used": False,
-          # MTTS_SIDE_REDUCE=1 (opt-in): once MTTS_SIDE_REDUCE_JOBS sums are queued, they run on a side
-          # stream while the backward continues, joined at the context exit.  Measured slower in the
-          # captured step (8.68 -> 9.25..9.39 ms for chunks of 12/24/48 jobs, same box), like the
-          # side-stream weight gradients: the default flushes once at the end
-          "side_on": os.environ.get("MTTS_SIDE_REDUCE", "0") == "1",
-          "chunk": int(os.environ.get("MTTS_SIDE_REDUCE_JOBS", "24")),
-          # > 0: flush on the MAIN stream once this many sums are queued (slabs re-read while still in the
-          # MALL instead of from HBM at the end of the backward).  0 (default since the weight-gradient GEMMs
-          # are queued too): one flush at the end -- the batched launches then hold the whole backward's
-          # weight gradients (same box: 8 -> 7.99 ms, 16 7.86, 32 7.77, 64 7.71, 128 7.70, end only 7.64)
-          "inline": int(os.environ.get("MTTS_INLINE_REDUCE_JOBS", "0"))}
-
-
 def _leaves(*ts) -> bool:
     return all(t is None or t.is_leaf for t in ts)
-
-
-def _keep_partials(*ts):
-    if _DEFER["on"]:
-        _DEFER["keep"].extend(t for t in ts if t is not None)
-
-
-@contextlib.contextmanager
-def deferred_grad_sums(enabled: bool = True):
-    if not enabled or _DEFER["on"]:
-        yield
-        return
-    lib = N.lib()
-    lib.mtts_defer_reductions(1)
-    _DEFER["on"] = True
-    _DEFER["seam"] = False
-    ok = False
-    try:
-        yield
-        ok = True
-    finally:
-        lib.mtts_defer_reductions(0)
-        _DEFER["on"] = False
-        try:
-            if ok:
-                N.check(lib.mtts_flush_reductions(torch.cuda.current_stream().cuda_stream), "mtts_flush_reductions")
-            else:
-                lib.mtts_discard_reductions()
-        finally:
-            _join_side_sums()
-            _DEFER["keep"].clear()  # stream-ordered frees, after the flush launch
-
-
-def _join_side_sums():
-    """The current stream waits for the side-stream sums; their partial slabs may then be freed."""
-    if _DEFER["side_used"]:
-        main = torch.cuda.current_stream()
-        for side in _DEFER["side"].values():
-            main.wait_stream(side)
-        _DEFER["side_used"] = False
-    _DEFER["side_keep"].clear()
-
-
-def _maybe_side_sums():
-    """Inside deferred_grad_sums(): once enough sums are queued, run them on a side stream (after the
-    main stream's work so far) while the backward goes on.  Their inputs (partial slabs, kept alive in
-    side_keep) and outputs (fresh parameter gradients, which autograd steals without a kernel and
-    nothing reads before the join) make this safe."""
-    if _DEFER["on"] and not _DEFER["side_on"] and _DEFER["inline"] > 0:
-        lib = N.lib()
-        if lib.mtts_pending_reductions() >= _DEFER["inline"]:
-            N.check(lib.mtts_flush_reductions(torch.cuda.current_stream().cuda_stream), "mtts_flush_reductions")
-            _DEFER["keep"].clear()  # stream-ordered frees, after the flush launch
-        return
-    if _DEFER["on"] and _DEFER["seam"] and _ENC_SIDE_JOBS > 0:
-        # past the decoder/encoder seam: the encoder's own queued gradients go to the side stream in chunks
-        # (MTTS_ENC_SIDE_JOBS), behind the decoder's batch there, instead of all at the end on the main one
-        if N.lib().mtts_pending_reductions() >= _ENC_SIDE_JOBS:
-            flush_deferred_side()
-        return
-    if not (_DEFER["on"] and _DEFER["side_on"]):
-        return
-    lib = N.lib()
-    if lib.mtts_pending_reductions() < _DEFER["chunk"]:
-        return
-    dev = torch.cuda.current_device()
-    side = _DEFER["side"].get(dev)
-    if side is None:
-        side = _DEFER["side"][dev] = torch.cuda.Stream(dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    N.check(lib.mtts_flush_reductions(side.cuda_stream), "mtts_flush_reductions")
-    _DEFER["side_keep"].extend(_DEFER["keep"])
-    _DEFER["keep"].clear()
-    _DEFER["side_used"] = True
-
-
-# MTTS_SIDE_FLUSH (default on): at the decoder -> encoder seam of the backward (flow_matching._CfmPack) the
-# decoder's queued weight gradients + sums are launched on a side stream, forked there and joined at the
-# deferral's exit, so their chip-filling batched launches overlap the text encoder's latency-bound backward
-_SIDE_FLUSH = os.environ.get("MTTS_SIDE_FLUSH", "1") != "0"
-# MTTS_SIDE_WGRAD_CAP: workgroups the side-flushed weight-gradient batch may occupy (0 = one per block):
-# fewer leave CUs to the encoder's backward on the main stream (mtts_wgrad_flush_cap)
-_SIDE_CAP = int(os.environ.get("MTTS_SIDE_WGRAD_CAP", "0"))
-# MTTS_ENC_SIDE_JOBS > 0: after the seam flush, side-flush again whenever this many sums are queued -- the
-# text encoder's own weight gradients then queue behind the decoder's batch on the side stream instead of
-# all running on the main one after the encoder's backward (same box: 0 -> 7.20 ms, 8 7.47, 16 7.22,
-# 24 7.12, 32 7.10, 40 7.14, 48 7.11, 64 7.11)
-_ENC_SIDE_JOBS = int(os.environ.get("MTTS_ENC_SIDE_JOBS", "32"))
-
-
-def flush_deferred_side() -> None:
-    """Inside deferred_grad_sums() (no-op outside, or with MTTS_SIDE_FLUSH=0): everything queued so far
-    -- the weight-gradient GEMMs, batched, then the sums -- runs on a side stream forked from the current
-    one here, while the backward continues on it; the deferral's exit (or the next main-stream flush)
-    joins it.  Inputs and slabs stay alive until then (side_keep); the outputs are fresh parameter
-    gradients that nothing reads before the join."""
-    if not (_DEFER["on"] and _SIDE_FLUSH) or _DEFER["side_on"]:
-        return
-    lib = N.lib()
-    if lib.mtts_pending_reductions() == 0:
-        return
-    dev = torch.cuda.current_device()
-    side = _DEFER["side"].get(dev)
-    if side is None:
-        side = _DEFER["side"][dev] = torch.cuda.Stream(dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    lib.mtts_wgrad_flush_cap(_SIDE_CAP)
-    try:
-        N.check(lib.mtts_flush_reductions(side.cuda_stream), "mtts_flush_reductions")
-    finally:
-        lib.mtts_wgrad_flush_cap(0)
-    _DEFER["side_keep"].extend(_DEFER["keep"])
-    _DEFER["keep"].clear()
-    _DEFER["side_used"] = True
-    _DEFER["seam"] = True
-
-
-def param_grad_side_stream():
-    """Inside deferred_grad_sums() with MTTS_SIDE_FLUSH: the deferral's side stream, already ordered after
-    the current stream, for backward work whose only outputs are fresh parameter gradients (joined at the
-    deferral's exit like the side flush); None otherwise.  The caller allocates on the current stream and
-    hands every tensor the side work reads to keep_for_side()."""
-    if not (_DEFER["on"] and _SIDE_FLUSH) or _DEFER["side_on"]:
-        return None
-    dev = torch.cuda.current_device()
-    side = _DEFER["side"].get(dev)
-    if side is None:
-        side = _DEFER["side"][dev] = torch.cuda.Stream(dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    _DEFER["side_used"] = True
-    return side
-
-
-side_fork = param_grad_side_stream  # the same fork, for forward work that runs ahead (prefetch)
-
-
-def side_fork_available() -> bool:
-    """Whether side_fork() would return a stream (without forking): lets a caller finish the main-stream work
-    the side work reads before the fork orders the side stream after it."""
-    return bool(_DEFER["on"] and _SIDE_FLUSH) and not _DEFER["side_on"]
-
-
-def keep_for_side(*ts) -> None:
-    _DEFER["side_keep"].extend(t for t in ts if t is not None)
-
-
-def flush_for_bucket():
-    """Inside deferred_grad_sums(), before a data-parallel bucket is packed: every queued weight gradient
-    and sum runs now -- on the deferral's side stream when the seam flush is on (the main stream goes on
-    with the backward; the seam overlap of the N=1 step is kept), else on the main stream.  Returns the side
-    stream whose work so far the packer must wait for (None: everything is ordered on the main stream)."""
-    if not _DEFER["on"]:
-        return None
-    if _SIDE_FLUSH and not _DEFER["side_on"]:
-        flush_deferred_side()
-        return _DEFER["side"].get(torch.cuda.current_device()) if _DEFER["side_used"] else None
-    flush_deferred_grad_sums()
-    return None
-
-
-def flush_deferred_grad_sums() -> None:
-    """Runs the queued parameter-gradient sums now (inside deferred_grad_sums(); no-op outside): the
-    data-parallel reducer calls it before packing a bucket, so the deferral still batches the sums of
-    each bucket into one launch."""
-    if not _DEFER["on"]:
-        return
-    _join_side_sums()
-    N.check(N.lib().mtts_flush_reductions(torch.cuda.current_stream().cuda_stream), "mtts_flush_reductions")
-    _DEFER["keep"].clear()  # stream-ordered frees, after the flush launch
-
-
-def _grad_sums(backward):
-    """Backward decorator: a Function with non-leaf weights sums its partials at once."""
-    @functools.wraps(backward)
-    def run(ctx, *grads):
-        if not _DEFER["on"]:
-            return backward(ctx, *grads)
-        if getattr(ctx, "leaf", True):
-            out = backward(ctx, *grads)
-            _maybe_side_sums()
-            return out
-        lib = N.lib()
-        lib.mtts_defer_reductions(0)
-        try:
-            return backward(ctx, *grads)
-        finally:
-            lib.mtts_defer_reductions(1)
-    return run
 
 
 # Data-parallel gradient slots: GradBucketReducer.arm() hands the flat all-reduce buffer's per-parameter views to
@@ -927,26 +683,6 @@ def _grad_buf_stacked(keys, shapes, rows, K, device):
 
 def _wgrad(dY, To_full, out_stride, out_off, A, Ti, To, nb, in_stride, offs, cin, N_, dw, strides, *, prec,
            a_scale=None, db=None, rows_per_step=-1, target_blocks=-1, depth=-1):
-    if _SIDE_WGRAD["on"] and dY.is_cuda:
-        dev = dY.device
-        side = _SIDE_WGRAD["streams"].get(dev)
-        if side is None:
-            side = _SIDE_WGRAD["streams"][dev] = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        # inputs only: an extra reference to dw / db would make AccumulateGrad clone them on the main
-        # stream (it steals a gradient only at use count 1) -- reading them before the side stream wrote
-        _SIDE_WGRAD["keep"].extend(t for t in (dY, A, a_scale) if t is not None)
-        with torch.cuda.stream(side):
-            return _wgrad_launch(dY, To_full, out_stride, out_off, A, Ti, To, nb, in_stride, offs, cin, N_, dw,
-                                 strides, prec=prec, a_scale=a_scale, db=db, rows_per_step=rows_per_step,
-                                 target_blocks=target_blocks, depth=depth)
-    return _wgrad_launch(dY, To_full, out_stride, out_off, A, Ti, To, nb, in_stride, offs, cin, N_, dw, strides,
-                         prec=prec, a_scale=a_scale, db=db, rows_per_step=rows_per_step,
-                         target_blocks=target_blocks, depth=depth)
-
-
-def _wgrad_launch(dY, To_full, out_stride, out_off, A, Ti, To, nb, in_stride, offs, cin, N_, dw, strides, *, prec,
-                  a_scale=None, db=None, rows_per_step=-1, target_blocks=-1, depth=-1):
     args = ConvWgradArgs()
     args.dY, args.ldy, args.To_full, args.out_stride, args.out_off = dY.data_ptr(), _ld(dY), To_full, out_stride, out_off
     args.A, args.a_scale, args.lda, args.Ti, args.To, args.nb = A.data_ptr(), N.ptr(a_scale), _ld(A), Ti, To, nb
@@ -959,7 +695,7 @@ def _wgrad_launch(dY, To_full, out_stride, out_off, A, Ti, To, nb, in_stride, of
                   | (WGRAD_F_DY_BF16 if dY.dtype == torch.bfloat16 else 0))
     lib = N.lib()
     ws = torch.empty(int(lib.mtts_conv_wgrad_workspace_size(ctypes.byref(args))), dtype=torch.uint8, device=dY.device)
-    # inside deferred_grad_sums() the GEMM itself may be queued (MTTS_DEFER_WGRAD, run batched at the next
+    # inside deferred_grad_sums() the GEMM itself is queued (run batched at the next
     # flush): its inputs stay alive until then, like the slabs
     _keep_partials(ws, dY, A, a_scale)
     log = WGRAD_LOG

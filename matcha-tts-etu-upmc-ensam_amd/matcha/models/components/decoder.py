@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from matcha import _native as N
+from matcha.models.components import _defer as D
 from matcha.models.components import _ops as O
 from matcha.models.components.transformer import BasicTransformerBlock
 
@@ -242,7 +243,7 @@ class Decoder(nn.Module):
         with torch.autocast("cuda", enabled=False):
             tt = t.detach().float().reshape(-1).contiguous()
             e = torch.empty((tt.numel(), self.time_embeddings.dim), dtype=torch.float32, device=tt.device)
-            O.keep_for_side(tt, e)
+            D.keep_for_side(tt, e)
             with torch.cuda.device(tt.device):
                 N.check(N.lib().mtts_time_embedding(N.ptr(tt), tt.numel(), self.time_embeddings.dim, 1000.0, N.ptr(e),
                                                     side.cuda_stream), "mtts_time_embedding")

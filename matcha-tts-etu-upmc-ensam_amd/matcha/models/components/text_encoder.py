@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from matcha import _native as N
+from matcha.models.components import _defer as D
 from matcha.models.components import _ops as O
 
 # MTTS_ENCODER_DX_LINK=0: autograd sums each encoder layer's two input gradients (A/B switch)
@@ -205,12 +206,9 @@ class Encoder(nn.Module):
         p = self.dropout_rate if self.training else 0.0
         if key_bias is None:
             key_bias = (m - 1.0) * 1e4  # masked_fill(-1e4) on padded keys
-        # every layer's stacked q|k|v bias from ONE concatenation (one launch instead of one per layer) --
-        # except with the opt-in side-stream weight gradients: the concatenation routes the bias gradients
-        # through autograd's SplitBackward, which reads them on the main stream while the side stream
-        # still writes them; per layer each bias gradient is a direct view
+        # every layer's stacked q|k|v bias from ONE concatenation (one launch instead of one per layer)
         layers = list(self.attention_layers)
-        if O._SIDE_WGRAD["on"] or not _ONE_BIAS_CAT:
+        if not _ONE_BIAS_CAT:
             qkv_biases = [None] * len(layers)
         else:
             qkv_biases = torch.cat([b for a in layers for b in (a.query_conv.bias, a.key_conv.bias, a.value_conv.bias)])
@@ -262,9 +260,9 @@ class _Embedding(torch.autograd.Function):
         # deferral's side stream, beside the final weight-gradient flush (outputs allocated here, inputs kept)
         # (only when the weight takes the gradient: a dropped output's memory could be reused under the side
         # kernel; and the output is not kept alive -- AccumulateGrad must steal it, not copy it)
-        side = O.param_grad_side_stream() if ctx.needs_input_grad[1] else None
+        side = D.param_grad_side_stream() if ctx.needs_input_grad[1] else None
         if side is not None:
-            O.keep_for_side(ids_c, gc)
+            D.keep_for_side(ids_c, gc)
         st = side.cuda_stream if side is not None else N.stream_handle(gc.device)
         with torch.cuda.device(gc.device):
             N.check(N.lib().mtts_embedding_bwd(N.ptr(ids_c), N.ptr(gc), ids_c.numel(), V, C, ctx.scale, N.ptr(dw),

@@ -19,6 +19,7 @@ import torch
 
 import matcha.utils.monotonic_align as monotonic_align
 from matcha.models.baselightningmodule import BaseLightningClass
+from matcha.models.components import _defer as D
 from matcha.models.components import _ops as O
 from matcha.models.components.flow_matching import ConditionalFlowMatching as CFM
 from matcha.models.components.text_encoder import TextEncoder
@@ -136,9 +137,9 @@ class MatchaTTS(BaseLightningClass):
         # instead of in compute_loss; the same distribution)
         # t is drawn BEFORE the fork: the side stream's time embedding reads it, and the fork orders the side
         # stream after the main stream's work up to that point only (drawn after it, the read raced the draw)
-        if x.is_cuda and _PREFETCH and t is None and O.side_fork_available():
+        if x.is_cuda and _PREFETCH and t is None and D.side_fork_available():
             t = torch.rand([x.shape[0], 1, 1], device=x.device, dtype=torch.float32)
-        side = O.side_fork() if (x.is_cuda and _PREFETCH) else None
+        side = D.side_fork() if (x.is_cuda and _PREFETCH) else None
         if side is not None:
             if t is None:
                 t = torch.rand([x.shape[0], 1, 1], device=x.device, dtype=torch.float32)

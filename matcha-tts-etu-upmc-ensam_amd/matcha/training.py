@@ -52,6 +52,7 @@ import torch.distributed as dist
 
 from matcha import _native as N
 from matcha.models.components import _ops as OPS
+from matcha.models.components._defer import deferred_grad_sums
 from matcha.models.matcha_tts import MatchaTTS
 
 
@@ -221,11 +222,6 @@ class TrainConfig:
 
 
 class Trainer:
-    # opt-in: measured in-step on MI355X the graph step got SLOWER with weight gradients on a side
-    # stream (round 1: 11.25 vs 11.01 ms; round 2: 9.43 vs 8.57 ms): the ~100 cross-stream edges cost
-    # more than the overlap returns
-    side_stream_wgrad = os.environ.get("MTTS_SIDE_WGRAD", "0") == "1"
-    defer_grad_sums = os.environ.get("MTTS_DEFER_GRAD_SUMS", "1") != "0"
     # MTTS_FORCE_DP=1: run the data-parallel exchange even at world size 1 (rehearses the bucketed
     # RCCL path on a one-GPU box; the all-reduce of one rank is a copy)
     force_dp = os.environ.get("MTTS_FORCE_DP", "0") == "1"
@@ -303,24 +299,18 @@ class Trainer:
             n = 1
         elif n > 1 and self._stash_ok():
             return self._fwd_bwd_stash(batches)
-        # weight gradients on a side stream, overlapping the dgrad chain (components/_ops.py
-        # side_stream_wgrad): safe when autograd steals every fresh gradient (graph step, one
-        # micro-batch, gradients set to None first); joined before this returns
+        # the parameter-gradient partial sums of the whole backward in batched launches
+        # (components/_defer.py deferred_grad_sums): needs fresh gradients, which autograd steals (one
+        # micro-batch, gradients set to None first), and no DDP hook reading them during the backward
+        # (the bucket reducer flushes the queue per bucket)
         fresh = n == 1 and self.dev.type == "cuda" and all(p.grad is None for p in self.params)
-        # (never with the DP reducer: it packs gradients on the main stream while the side stream may
-        # still be writing them)
-        side = self.cfg.graph and fresh and self.side_stream_wgrad and not self.dp
-        # the parameter-gradient partial sums of the whole backward in one batched launch
-        # (components/_ops.py deferred_grad_sums): also needs fresh gradients, and no DDP hook
-        # reading them during the backward (the bucket reducer flushes the queue per bucket)
-        defer = fresh and self.defer_grad_sums and not side and (self.cfg.graph or self.dp_mode != "ddp")
+        defer = fresh and (self.cfg.graph or self.dp_mode != "ddp")
         # several micro-batches (accumulate_grad_batches): the FIRST one's gradients are fresh too -- its
         # backward runs deferred (batched weight gradients, flushed when it ends, before the next micro-batch
         # accumulates into them); the later ones accumulate and run per layer
-        self._defer_first = (n > 1 and self.dev.type == "cuda" and self.defer_grad_sums
-                             and all(p.grad is None for p in self.params)
+        self._defer_first = (n > 1 and self.dev.type == "cuda" and all(p.grad is None for p in self.params)
                              and (self.cfg.graph or self.dp_mode != "ddp"))
-        with OPS.deferred_grad_sums(defer), OPS.side_stream_wgrad(side):
+        with deferred_grad_sums(defer):
             return self._fwd_bwd_body(batches, sync_ctx)
 
     def _merge_ok(self, batches) -> bool:
@@ -342,8 +332,7 @@ class Trainer:
         path (batched, deferred weight gradients and sums, side-stream seam flushes) -- its gradients are
         stashed and summed at the end instead of accumulated per layer.  The DP reducer packs the last
         micro-batch's gradients as backward produces them, so it keeps the accumulating path."""
-        return (self.dev.type == "cuda" and not self.dp and self.defer_grad_sums
-                and all(p.grad is None for p in self.params))
+        return self.dev.type == "cuda" and not self.dp and all(p.grad is None for p in self.params)
 
     def _fwd_bwd_stash(self, batches):
         """Micro-batch i: forward + (total / n).backward() on fresh gradients under the gradient deferral (the
@@ -355,7 +344,7 @@ class Trainer:
         logged = None
         stash = []
         for i, batch in enumerate(batches):
-            with OPS.deferred_grad_sums(True):
+            with deferred_grad_sums(True):
                 vals = self._fwd_bwd_body([batch], div=n)
             logged = vals if logged is None else logged + vals
             stash.append([p.grad for p in self.params])
@@ -383,7 +372,7 @@ class Trainer:
         logged = None
         for i, batch in enumerate(batches):
             ctx = sync_ctx(i) if sync_ctx else contextlib.nullcontext()
-            first = OPS.deferred_grad_sums(True) if (i == 0 and getattr(self, "_defer_first", False)) \
+            first = deferred_grad_sums(True) if (i == 0 and getattr(self, "_defer_first", False)) \
                 else contextlib.nullcontext()
             with ctx, first:
                 inject = {k: batch[k] for k in ("t", "z") if k in batch}  # parity tests' CFM randomness

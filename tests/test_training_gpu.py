@@ -69,51 +69,26 @@ def test_graph_replays_draw_new_dropout_masks():
     assert len({round(v, 6) for v in losses[:, 2].tolist()}) > 1  # diff loss changes (t, z, masks)
 
 
-def test_side_stream_wgrad_matches_main_stream():
-    """Weight gradients launched on the side stream (components/_ops.py side_stream_wgrad) equal the
-    main-stream ones: same kernels, same inputs -- only the ordering against the dgrad chain moves."""
-    from matcha.models.components import _ops as OPS
-    from matcha.training import synthetic_batch
-
-    b = synthetic_batch(4, 20, 80, device=DEV)
-    m = _model(2)
-    m.eval()
-    t = torch.rand(4, 1, 1, device=DEV)
-    z = torch.randn(4, 80, 80, device=DEV)
-
-    def grads(side):
-        m.zero_grad(set_to_none=True)
-        with OPS.side_stream_wgrad(side):
-            dur, prior, diff, _ = m(**b, t=t, z=z)
-            (dur + prior + diff).backward()
-        torch.cuda.synchronize()
-        return {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
-
-    g0, g1 = grads(False), grads(True)
-    assert g0.keys() == g1.keys() and len(g0) > 100
-    for n in g0:  # every gradient comes from libmtts (incl. the embedding's fixed-order backward): bitwise
-        assert torch.equal(g1[n], g0[n]), n
-
-
-@pytest.mark.parametrize("side", [False, True, "inline", "cap", "enc_chunks"])
-def test_deferred_grad_sums_match_immediate(side):
+@pytest.mark.parametrize("mode", [False, "cap", "enc_chunks", "default"])
+def test_deferred_grad_sums_match_immediate(mode):
     """The deferred weight-gradient GEMMs (launched batched, csrc/conv_gemm.hip) and parameter-gradient sums
-    (csrc/reduce.hip) equal the per-layer ones bitwise on the decoder (same row splits, same fixed-order
-    sums, a few launches instead of one or two per layer); side: batches of them run on a side stream while
-    the backward goes on (joined at the context exit); "inline": batches of 8 flushed on the main stream as
-    they queue up (MTTS_INLINE_REDUCE_JOBS; the default flushes once, at the end)."""
+    (csrc/reduce.hip) equal the per-layer ones bitwise (same row splits, same fixed-order sums, a few launches
+    instead of one or two per layer).  False: the decoder's batch goes to the side stream at the seam, the
+    encoder's sums stay queued until the exit; "cap": the same on a capped grid; "enc_chunks": the encoder's
+    sums follow on the side stream every 16; "default": the production chunk size (components/_defer.py)."""
     from matcha import _native as N
-    from matcha.models.components import _ops as OPS
+    from matcha.models.components._defer import DEFER, deferred_grad_sums
     from matcha.training import synthetic_batch
 
-    inline = side == "inline"
-    cap = side == "cap"  # batched weight-gradient launches on a capped grid (37 workgroups walk the blocks)
-    side = side is True
-    saved_inline, saved_enc = OPS._DEFER["inline"], OPS._ENC_SIDE_JOBS
-    OPS._DEFER["side_on"], OPS._DEFER["chunk"], OPS._DEFER["inline"] = side, 8, (8 if inline else 0)
-    # the encoder's chunked side flushes (default) would empty the queue the plain mode checks; "enc_chunks"
-    # keeps them (every 16 sums) and checks only the bitwise equality
-    OPS._ENC_SIDE_JOBS = 16 if side == "enc_chunks" else 0
+    cap = mode == "cap"  # batched weight-gradient launches on a capped grid (37 workgroups walk the blocks)
+    plain = mode in (False, "cap")
+    saved_enc = DEFER.enc_side_jobs
+    # the encoder's chunked side flushes would empty the queue the plain modes check: never reached there;
+    # "enc_chunks" runs them every 16 sums, "default" leaves the production value
+    if plain:
+        DEFER.enc_side_jobs = 1 << 30
+    elif mode == "enc_chunks":
+        DEFER.enc_side_jobs = 16
     # queued weight gradients run batched with the batched split plan: the immediate pass takes the same
     # plan, so the comparison isolates the batching (one launch for many layers) and the deferral
     N.lib().mtts_wgrad_plan_mode(1)
@@ -127,24 +102,21 @@ def test_deferred_grad_sums_match_immediate(side):
     def grads(defer):
         m.zero_grad(set_to_none=True)
         N.lib().mtts_wgrad_flush_cap(37 if (cap and defer) else 0)
-        with OPS.deferred_grad_sums(defer):
+        with deferred_grad_sums(defer):
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 dur, prior, diff, _ = m(**b, t=t, z=z)
             (dur + prior + diff).backward()
-            if defer and not side and not inline and OPS._ENC_SIDE_JOBS == 0:
+            if defer and plain:
                 assert N.lib().mtts_pending_reductions() > 50  # queued, not yet run
-            if defer and inline:
-                assert N.lib().mtts_pending_reductions() < 8  # flushed in batches during the backward
-            if defer and side:
-                assert OPS._DEFER["side_used"]  # some batches already launched on the side stream
+            if defer and not plain:
+                assert DEFER.side_used  # batches already launched on the side stream
         torch.cuda.synchronize()
         return {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
 
     try:
         g0, g1 = grads(False), grads(True)
     finally:
-        OPS._DEFER["side_on"], OPS._DEFER["chunk"], OPS._DEFER["inline"] = False, 24, saved_inline
-        OPS._ENC_SIDE_JOBS = saved_enc
+        DEFER.enc_side_jobs = saved_enc
         N.lib().mtts_wgrad_plan_mode(0)
         N.lib().mtts_wgrad_flush_cap(0)
     assert N.lib().mtts_pending_reductions() == 0
