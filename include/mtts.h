@@ -42,7 +42,7 @@ extern "C" {
 typedef enum mtts_status {
     MTTS_OK = 0,
     MTTS_ERR_INVALID_ARG = -1, /* null pointer, negative size, bad flag */
-    MTTS_ERR_SHAPE = -2,       /* shape outside what the kernels support (e.g. Tx > 4096) */
+    MTTS_ERR_SHAPE = -2,       /* shape outside what the kernels support (e.g. Tx > 8192) */
     MTTS_ERR_WORKSPACE = -3,   /* workspace too small */
     MTTS_ERR_HIP = -4,         /* a HIP runtime call failed (launch, attribute) */
     MTTS_ERR_UNSUPPORTED = -5  /* feature not built into this library */
@@ -62,7 +62,7 @@ const char *mtts_last_error(void);
 
 /* Maximum text length (Tx) the kernels accept. */
 #define MTTS_MAS_MAX_TX 8192 /* maximum_path / the fused prior path (transposed lattice): 8 waves x 16 text rows per lane of
-                                the multi-wave DP (round 6; 4096 in rounds 4-5; 2048 with MTTS_MAS_MW=0) */
+                                the multi-wave DP (round 6; 4096 in rounds 4-5) */
 #define MTTS_MAS_MAX_TX_ROW_MAJOR 4096 /* mtts_compute_batch_alignments (the row-major lattice it mutates): 8 x 8 rows */
 
 /* Bytes of device workspace mtts_maximum_path_f32 / mtts_compute_batch_alignments need. */

@@ -26,10 +26,8 @@
 // diagonal (`from_prev >= from_same or x == y`, core.pyx:73), out-of-band cells hold max_neg_val.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -38,7 +36,12 @@
 namespace {
 
 constexpr int kWave = 64;
-constexpr int kDefaultRing = 2;  // lattice chunks in the DP ring (premasked); 3 and 4 measured equal (DP is VALU-chain bound)
+// Lattice chunks in the one-wave DP's ring (mas_dp_kernel's D).  The depth sweeps are closed ("MAS: the
+// sweeps are closed"; profiles/r04/mas/sweep.jsonl), the depths they chose are fixed here:
+constexpr int kDefaultRing = 2;  // row-major, premasked: 3 and 4 measured equal (DP is VALU-chain bound)
+constexpr int kMaskedRing = 2;   // row-major, value and mask streams (a register ring each; never swept)
+constexpr int kTrRing = 4;       // transposed: 8 x 256 x 2048 0.249 ms; depth 2 / 8: 0.260 / 0.288 (1,0-ring2 / -ring8)
+constexpr int kMwWaves = 8;      // waves per utterance of the multi-wave DP (mas_dp_mw_kernel's W)
 constexpr int kLdsBitsLimit = 48 * 1024;  // LDS bytes for backpointer words (total stays <= 64 KiB)
 
 struct MasArgs {
@@ -1257,63 +1260,23 @@ bool tr_enabled(int Tx) {
     return Tx > 128;
 }
 
-// lattice chunks in flight for the one-wave DP on the transposed lattice (MTTS_MAS_TR_RING: 2 / 4 / 8)
-int tr_ring() {
-    static const int d = [] {
-        const char *e = getenv("MTTS_MAS_TR_RING");
-        const int v = e ? atoi(e) : 0;
-        return (v == 2 || v == 4 || v == 8) ? v : 4;
-    }();
-    return d;
-}
-
-// MTTS_MAS_MW=0: the one-wave DP for every Tx (A/B; Tx <= 2048 then)
-bool mw_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("MTTS_MAS_MW");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// shape_override: MTTS_MAS_SHAPE may pick the DP shape -- only where the DP reads the transposed lattice (the
-// row-major kernels reject several of the shapes it can name: ADVICE r4)
-WsLayout ws_layout(int B, int Tx, int Ty, bool with_lat = false, bool shape_override = true) {
+// The DP shape for text length Tx: the one-wave kernel at K = 1 / 2 / 4 rows per lane to Tx = 256, kMwWaves waves x
+// KL = 1 / 2 / 4 / 8 / 16 rows per lane above: the multi-wave DP where it measured faster (tools/mas_bench.py,
+// profiles/r04/sweeps/mas_*.jsonl: 8 x 512 x 4096 0.93 vs 0.99 ms); at Tx <= 256 the one-wave kernel is faster
+// (120 x 600: 65 vs 72 us; 256 x 2048: 280 vs 319 us) -- the per-column dependency chain, not the rows per lane,
+// bounds both.  The round-4 sweep of 2- and 4-wave shapes found none more than 4 % ahead of this policy (DESIGN.md,
+// the shape table; profiles/r04/mas/sweep.jsonl) and is closed: those shapes are no longer built.
+WsLayout ws_layout(int B, int Tx, int Ty, bool with_lat = false) {
     WsLayout w{};
     w.W = 1;
     w.KL = 1;
-    w.K = Tx <= 64 ? 1 : Tx <= 128 ? 2 : Tx <= 256 ? 4 : Tx <= 512 ? 8 : Tx <= 1024 ? 16 : 32;
-    w.Txp = kWave * w.K;
-    // the multi-wave DP where it measured faster (tools/mas_bench.py, profiles/r04/sweeps/mas_*.jsonl: 8 x 512 x 4096
-    // 0.93 vs 0.99 ms) or where the one-wave one cannot go (Tx > 2048); at Tx <= 256 the one-wave kernel is faster
-    // (120 x 600: 65 vs 72 us; 256 x 2048: 280 vs 319 us) -- the per-column dependency chain, not the rows per
-    // lane, bounds both
-    if (Tx > 256 && mw_enabled()) {
-        w.W = 8;
+    w.K = Tx <= 64 ? 1 : Tx <= 128 ? 2 : 4;
+    if (Tx > 256) {
+        w.W = kMwWaves;
         w.KL = Tx <= 512 ? 1 : Tx <= 1024 ? 2 : Tx <= 2048 ? 4 : Tx <= 4096 ? 8 : 16;  // (16: transposed lattice only)
         w.K = w.W * w.KL;
-        w.Txp = kWave * w.K;
     }
-    // MTTS_MAS_SHAPE="W,KL" (tuning sweeps, transposed-lattice DP only -- every lattice but the core.pyx API's):
-    // W waves x KL rows per lane; W = 1 the one-wave kernel (K from Tx).  Ignored unless it covers Tx.
-    if (const char *e = shape_override ? getenv("MTTS_MAS_SHAPE") : nullptr) {
-        int W = 0, KL = 0;
-        if (sscanf(e, "%d,%d", &W, &KL) == 2 && tr_enabled(Tx)) {
-            const bool ok1 = W == 1;
-            const bool okm = (W == 2 && (KL == 1 || KL == 2)) || (W == 4 && (KL == 1 || KL == 2 || KL == 4)) ||
-                             (W == 8 && (KL == 1 || KL == 2 || KL == 4 || KL == 8));
-            if (ok1 && Tx <= 2048) {
-                w.W = w.KL = 1;
-                w.K = Tx <= 64 ? 1 : Tx <= 128 ? 2 : Tx <= 256 ? 4 : Tx <= 512 ? 8 : Tx <= 1024 ? 16 : 32;
-                w.Txp = kWave * w.K;
-            } else if (okm && kWave * W * KL >= Tx) {
-                w.W = W;
-                w.KL = KL;
-                w.K = W * KL;
-                w.Txp = kWave * w.K;
-            }
-        }
-    }
+    w.Txp = kWave * w.K;
     w.nch = (Ty + 31) / 32;
     w.lds_bits = (size_t)w.Txp * w.nch * 4 <= (size_t)kLdsBitsLimit;
     size_t off = 0;
@@ -1345,184 +1308,86 @@ bool mw_lds_attr(K kernel, size_t bytes) {
                                (int)bytes) == hipSuccess;
 }
 
-template <int KL, int W, bool PM>
+// Runtime bools to template arguments: dispatch_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...)
+template <class F>
+int dispatch_bools(F &&f) {
+    return f();
+}
+template <class F, class... Rest>
+int dispatch_bools(F &&f, bool b, Rest... rest) {
+    auto bind = [&](auto bc) { return dispatch_bools([&](auto... r) { return f(bc, r...); }, rest...); };
+    return b ? bind(std::true_type{}) : bind(std::false_type{});
+}
+
+// The kernel variants that exist, for both DP kernels: calls f(PM, VEC, LDS_BITS, DP_OUT, TR) as bool constants.
+//   transposed lattice (a.tr_ld > 0): premasked, column loads (no VEC), no dp_out -- LDS or global bits
+//   row-major, value and mask:        no dp_out (the mutated lattice is the premasked core.pyx API's)
+//   row-major, premasked:             every VEC x LDS_BITS x DP_OUT
+template <class F>
+int dispatch_variant(const MasArgs &a, bool vec, bool lds_bits, bool dp_out, F &&f) {
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (a.tr_ld > 0) {
+        if (dp_out) return mtts::fail(MTTS_ERR_INVALID_ARG, "maximum_path: dp_out needs the row-major lattice");
+        return dispatch_bools([&](auto l) { return f(yes, no, l, no, yes); }, lds_bits);
+    }
+    if (!a.premasked) {
+        if (dp_out) return mtts::fail(MTTS_ERR_INVALID_ARG, "maximum_path: dp_out needs a premasked lattice");
+        return dispatch_bools([&](auto v, auto l) { return f(no, v, l, no, no); }, vec, lds_bits);
+    }
+    return dispatch_bools([&](auto v, auto l, auto d) { return f(yes, v, l, d, no); }, vec, lds_bits, dp_out);
+}
+
+template <int K, int C>
+int launch_dp_one(const MasArgs &a, int B, bool vec, bool lds_bits, bool dp_out, size_t shmem, hipStream_t st) {
+    return dispatch_variant(a, vec, lds_bits, dp_out, [&](auto pm, auto v, auto l, auto d, auto tr) {
+        constexpr int D = tr ? kTrRing : pm ? kDefaultRing : kMaskedRing;
+        hipLaunchKernelGGL((mas_dp_kernel<K, C, D, pm, v, l, d, tr>), dim3(B), dim3(kWave), shmem, st, a);
+        return mtts::check_launch("mas_dp_kernel");
+    });
+}
+
+template <int KL>
 int launch_dp_mw(MasArgs a, int B, bool vec, bool lds_bits, bool dp_out, size_t shmem, hipStream_t st) {
-    dim3 grid(B), block(64 * W);
     if (!lds_bits) shmem = mw_backtrack_bufs(a, shmem);
-#define MTTS_MAS_MW_LAUNCH(V, L, DO)                                                                  \
-    do {                                                                                              \
-        if (!mw_lds_attr(mas_dp_mw_kernel<KL, W, PM, V, L, DO && PM>, shmem))                         \
-            return mtts::fail(MTTS_ERR_HIP, "maximum_path: LDS attribute");                           \
-        hipLaunchKernelGGL((mas_dp_mw_kernel<KL, W, PM, V, L, DO && PM>), grid, block, shmem, st, a); \
-    } while (0)
-    if (vec) {
-        if (lds_bits) {
-            if (dp_out) MTTS_MAS_MW_LAUNCH(true, true, true); else MTTS_MAS_MW_LAUNCH(true, true, false);
-        } else {
-            if (dp_out) MTTS_MAS_MW_LAUNCH(true, false, true); else MTTS_MAS_MW_LAUNCH(true, false, false);
-        }
-    } else {
-        if (lds_bits) {
-            if (dp_out) MTTS_MAS_MW_LAUNCH(false, true, true); else MTTS_MAS_MW_LAUNCH(false, true, false);
-        } else {
-            if (dp_out) MTTS_MAS_MW_LAUNCH(false, false, true); else MTTS_MAS_MW_LAUNCH(false, false, false);
-        }
-    }
-#undef MTTS_MAS_MW_LAUNCH
-    return mtts::check_launch("mas_dp_mw_kernel");
-}
-
-template <int KL, int W>
-int launch_dp_mw_pm(const MasArgs &a, int B, bool vec, bool lds_bits, bool dp_out, size_t shmem, hipStream_t st) {
-    if (!a.premasked) {
-        if (dp_out) return mtts::fail(MTTS_ERR_INVALID_ARG, "maximum_path: dp_out needs a premasked lattice");
-        return launch_dp_mw<KL, W, false>(a, B, vec, lds_bits, false, shmem, st);
-    }
-    return launch_dp_mw<KL, W, true>(a, B, vec, lds_bits, dp_out, shmem, st);
-}
-
-template <int K, int C, int D, bool PM>
-int launch_dp_k(const MasArgs &a, int B, bool vec, bool lds_bits, bool dp_out, size_t shmem, hipStream_t st) {
-    dim3 grid(B), block(kWave);
-#define MTTS_MAS_LAUNCH(V, L, DO) \
-    hipLaunchKernelGGL((mas_dp_kernel<K, C, D, PM, V, L, DO && PM>), grid, block, shmem, st, a)
-    if (vec) {
-        if (lds_bits) {
-            if (dp_out) MTTS_MAS_LAUNCH(true, true, true); else MTTS_MAS_LAUNCH(true, true, false);
-        } else {
-            if (dp_out) MTTS_MAS_LAUNCH(true, false, true); else MTTS_MAS_LAUNCH(true, false, false);
-        }
-    } else {
-        if (lds_bits) {
-            if (dp_out) MTTS_MAS_LAUNCH(false, true, true); else MTTS_MAS_LAUNCH(false, true, false);
-        } else {
-            if (dp_out) MTTS_MAS_LAUNCH(false, false, true); else MTTS_MAS_LAUNCH(false, false, false);
-        }
-    }
-#undef MTTS_MAS_LAUNCH
-    return mtts::check_launch("mas_dp_kernel");
-}
-
-// Chunk shape and ring depth per rows-per-lane K: K*C = 32 cells per lane per chunk; the premasked
-// lattice (the fused training path and core.pyx's API) carries no mask registers, so it affords a
-// deeper ring.  MTTS_MAS_RING overrides the premasked depth (tuning).
-int ring_depth() {
-    static const int d = [] {
-        const char *e = getenv("MTTS_MAS_RING");
-        const int v = e ? atoi(e) : 0;
-        return (v == 2 || v == 3 || v == 4) ? v : 0;
-    }();
-    return d;
-}
-
-template <int K, int C>
-int launch_dp_kc(const MasArgs &a, int B, bool vec, bool lds_bits, bool dp_out, size_t shmem, hipStream_t st) {
-    if (!a.premasked) {
-        if (dp_out) return mtts::fail(MTTS_ERR_INVALID_ARG, "maximum_path: dp_out needs a premasked lattice");
-        return launch_dp_k<K, C, 2, false>(a, B, vec, lds_bits, false, shmem, st);
-    }
-    const int d = ring_depth() ? ring_depth() : kDefaultRing;
-    if (d == 2) return launch_dp_k<K, C, 2, true>(a, B, vec, lds_bits, dp_out, shmem, st);
-    if (d == 3) return launch_dp_k<K, C, 3, true>(a, B, vec, lds_bits, dp_out, shmem, st);
-    return launch_dp_k<K, C, 4, true>(a, B, vec, lds_bits, dp_out, shmem, st);
-}
-
-template <int KL, int W>
-int launch_dp_mw_tr(MasArgs a, int B, bool lds_bits, size_t shmem, hipStream_t st) {
-    if (!lds_bits) shmem = mw_backtrack_bufs(a, shmem);
-    if constexpr (KL <= 8) {  // (KL = 16: Txp = 8192 rows never fit the LDS-bits budget)
-        if (lds_bits) {
-            if (!mw_lds_attr(mas_dp_mw_kernel<KL, W, true, false, true, false, true>, shmem))
-                return mtts::fail(MTTS_ERR_HIP, "maximum_path: LDS attribute");
-            hipLaunchKernelGGL((mas_dp_mw_kernel<KL, W, true, false, true, false, true>), dim3(B), dim3(64 * W), shmem, st, a);
+    return dispatch_variant(a, vec, lds_bits, dp_out, [&](auto pm, auto v, auto l, auto d, auto tr) {
+        // KL = 16 (Tx > 4096) exists on the transposed lattice only, and there with global bits only (launch_dp)
+        if constexpr (KL <= 8 || (tr && !l)) {
+            const auto kernel = mas_dp_mw_kernel<KL, kMwWaves, pm, v, l, d, tr>;
+            if (!mw_lds_attr(kernel, shmem)) return mtts::fail(MTTS_ERR_HIP, "maximum_path: LDS attribute");
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * kMwWaves), shmem, st, a);
             return mtts::check_launch("mas_dp_mw_kernel");
-        }
-    }
-    {
-        if (!mw_lds_attr(mas_dp_mw_kernel<KL, W, true, false, false, false, true>, shmem))
-            return mtts::fail(MTTS_ERR_HIP, "maximum_path: LDS attribute");
-        hipLaunchKernelGGL((mas_dp_mw_kernel<KL, W, true, false, false, false, true>), dim3(B), dim3(64 * W), shmem, st, a);
-    }
-    return mtts::check_launch("mas_dp_mw_kernel");
-}
-
-template <int K, int C, int D>
-int launch_dp_k_tr(const MasArgs &a, int B, bool lds_bits, size_t shmem, hipStream_t st) {
-    if (lds_bits)
-        hipLaunchKernelGGL((mas_dp_kernel<K, C, D, true, false, true, false, true>), dim3(B), dim3(kWave), shmem, st, a);
-    else
-        hipLaunchKernelGGL((mas_dp_kernel<K, C, D, true, false, false, false, true>), dim3(B), dim3(kWave), shmem, st, a);
-    return mtts::check_launch("mas_dp_kernel");
-}
-
-template <int K, int C>
-int launch_dp_kc_tr(const MasArgs &a, int B, bool lds_bits, size_t shmem, hipStream_t st) {
-    const int d = tr_ring();
-    if (d == 2) return launch_dp_k_tr<K, C, 2>(a, B, lds_bits, shmem, st);
-    if (d == 8) return launch_dp_k_tr<K, C, 8>(a, B, lds_bits, shmem, st);
-    return launch_dp_k_tr<K, C, 4>(a, B, lds_bits, shmem, st);
-}
-
-// The DP on the transposed premasked lattice (a.tr_ld > 0): same kernels, column-major loads
-int launch_dp_tr(const MasArgs &a, int B, const WsLayout &w, hipStream_t st) {
-    if (w.W > 1) {
-        const size_t shmem = (size_t)w.Txp * 4 + (size_t)kEdgeRing * w.W * 32 * 4 + (w.lds_bits ? (size_t)w.Txp * w.nch * 4 : 0);
-        if (w.W == 2) return w.KL == 2 ? launch_dp_mw_tr<2, 2>(a, B, w.lds_bits, shmem, st)
-                                       : launch_dp_mw_tr<1, 2>(a, B, w.lds_bits, shmem, st);
-        if (w.W == 4) return w.KL == 4   ? launch_dp_mw_tr<4, 4>(a, B, w.lds_bits, shmem, st)
-                             : w.KL == 2 ? launch_dp_mw_tr<2, 4>(a, B, w.lds_bits, shmem, st)
-                                         : launch_dp_mw_tr<1, 4>(a, B, w.lds_bits, shmem, st);
-        switch (w.KL) {
-            case 1: return launch_dp_mw_tr<1, 8>(a, B, w.lds_bits, shmem, st);
-            case 2: return launch_dp_mw_tr<2, 8>(a, B, w.lds_bits, shmem, st);
-            case 4: return launch_dp_mw_tr<4, 8>(a, B, w.lds_bits, shmem, st);
-            case 8: return launch_dp_mw_tr<8, 8>(a, B, w.lds_bits, shmem, st);
-            default: return launch_dp_mw_tr<16, 8>(a, B, false, shmem, st);  // Tx <= 8192 (global bits)
-        }
-    }
-    const size_t shmem = (size_t)w.Txp * 4 + (w.lds_bits ? (size_t)w.Txp * w.nch * 4 : 0);
-    switch (w.K) {
-        case 1: return launch_dp_kc_tr<1, 32>(a, B, w.lds_bits, shmem, st);
-        case 2: return launch_dp_kc_tr<2, 16>(a, B, w.lds_bits, shmem, st);
-        case 4: return launch_dp_kc_tr<4, 8>(a, B, w.lds_bits, shmem, st);
-        case 8: return launch_dp_kc_tr<8, 4>(a, B, w.lds_bits, shmem, st);
-        case 16: return launch_dp_kc_tr<16, 2>(a, B, w.lds_bits, shmem, st);
-        default: return launch_dp_kc_tr<32, 1>(a, B, w.lds_bits, shmem, st);
-    }
-}
-
-int launch_dp(MasArgs a, int B, const WsLayout &w, bool vec, bool dp_out, hipStream_t st) {
-    if (a.tr_ld > 0) return dp_out ? mtts::fail(MTTS_ERR_INVALID_ARG, "maximum_path: dp_out needs the row-major lattice")
-                                   : launch_dp_tr(a, B, w, st);
-    if (w.W > 1) {
-        const size_t shmem = (size_t)w.Txp * 4 + (size_t)kEdgeRing * w.W * 32 * 4 + (w.lds_bits ? (size_t)w.Txp * w.nch * 4 : 0);
-        if (w.W < 8 && w.KL != 1) return mtts::fail(MTTS_ERR_UNSUPPORTED, "maximum_path: DP shape needs the transposed lattice");
-        if (w.KL > 8)
+        } else {
             return mtts::fail(MTTS_ERR_SHAPE, "maximum_path: Tx > 4096 needs the transposed lattice (compute_batch_alignments / "
                                               "dp_out and MTTS_MAS_TR=0 keep the row-major lattice: Tx <= 4096)");
-        if (w.W == 2) return launch_dp_mw_pm<1, 2>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-        if (w.W == 4) return launch_dp_mw_pm<1, 4>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-        switch (w.KL) {
-            case 1: return launch_dp_mw_pm<1, 8>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-            case 2: return launch_dp_mw_pm<2, 8>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-            case 4: return launch_dp_mw_pm<4, 8>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-            default: return launch_dp_mw_pm<8, 8>(a, B, vec, w.lds_bits, dp_out, shmem, st);  // Tx <= 4096
+        }
+    });
+}
+
+int launch_dp(const MasArgs &a, int B, const WsLayout &w, bool vec, bool dp_out, hipStream_t st) {
+    const size_t bits_lds = w.lds_bits ? (size_t)w.Txp * w.nch * 4 : 0;
+    if (w.W == 1) {
+        const size_t shmem = (size_t)w.Txp * 4 + bits_lds;
+        switch (w.K) {
+            case 1: return launch_dp_one<1, 32>(a, B, vec, w.lds_bits, dp_out, shmem, st);
+            case 2: return launch_dp_one<2, 16>(a, B, vec, w.lds_bits, dp_out, shmem, st);
+            default: return launch_dp_one<4, 8>(a, B, vec, w.lds_bits, dp_out, shmem, st);  // Tx <= 256
         }
     }
-    size_t shmem = (size_t)w.Txp * 4 + (w.lds_bits ? (size_t)w.Txp * w.nch * 4 : 0);
-    switch (w.K) {
-        case 1: return launch_dp_kc<1, 32>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-        case 2: return launch_dp_kc<2, 16>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-        case 4: return launch_dp_kc<4, 8>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-        case 8: return launch_dp_kc<8, 4>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-        case 16: return launch_dp_kc<16, 2>(a, B, vec, w.lds_bits, dp_out, shmem, st);
-        default: return launch_dp_kc<32, 1>(a, B, vec, w.lds_bits, dp_out, shmem, st);  // Tx <= 2048
+    const size_t shmem = (size_t)w.Txp * 4 + (size_t)kEdgeRing * w.W * 32 * 4 + bits_lds;
+    switch (w.KL) {
+        case 1: return launch_dp_mw<1>(a, B, vec, w.lds_bits, dp_out, shmem, st);
+        case 2: return launch_dp_mw<2>(a, B, vec, w.lds_bits, dp_out, shmem, st);
+        case 4: return launch_dp_mw<4>(a, B, vec, w.lds_bits, dp_out, shmem, st);
+        case 8: return launch_dp_mw<8>(a, B, vec, w.lds_bits, dp_out, shmem, st);  // Tx <= 4096
+        // Tx <= 8192: global bits (Txp = 8192 rows fit the LDS-bits budget at Ty <= 32 only)
+        default: return launch_dp_mw<16>(a, B, vec, false, dp_out, shmem, st);
     }
 }
 
 int check_shape(int B, int Tx, int Ty) {
     if (B < 0 || Tx < 1 || Ty < 1) return mtts::fail(MTTS_ERR_INVALID_ARG, "maximum_path: bad shape");
-    if (Tx > MTTS_MAS_MAX_TX || (Tx > 2048 && !mw_enabled()))
+    if (Tx > MTTS_MAS_MAX_TX)
         return mtts::fail(MTTS_ERR_SHAPE, "maximum_path: Tx > MTTS_MAS_MAX_TX (8192) is not supported");
     if ((int64_t)Tx * Ty * 4 >= (int64_t)1 << 31)
         return mtts::fail(MTTS_ERR_SHAPE, "maximum_path: one utterance's lattice exceeds 2 GiB");
@@ -1534,7 +1399,7 @@ int check_shape(int B, int Tx, int Ty) {
 extern "C" size_t mtts_maximum_path_workspace_size(int32_t B, int32_t Tx, int32_t Ty) {
     if (B < 0 || Tx < 1 || Ty < 1) return 0;
     // covers maximum_path (transposed lattice where tr_enabled) and compute_batch_alignments (row-major)
-    return std::max(ws_layout(B, Tx, Ty, true).total, ws_layout(B, Tx, Ty, true, false).total);
+    return ws_layout(B, Tx, Ty, true).total;
 }
 
 extern "C" int mtts_maximum_path_f32(const float *value, const float *mask, float *path, int32_t B,
@@ -1590,13 +1455,10 @@ extern "C" int mtts_maximum_path_f32(const float *value, const float *mask, floa
 
 extern "C" size_t mtts_prior_maximum_path_workspace_size(int32_t B, int32_t Tx, int32_t Ty) {
     if (B < 0 || Tx < 1 || Ty < 1) return 0;
-    size_t n = 0;
-    for (const bool tr : {true, false}) {  // the layout of either lattice (the call may pass lattice_out or not)
-        const WsLayout w = ws_layout(B, Tx, Ty, false, tr);  // lattice: row-major [B,Tx,Ty] or transposed [B,Ty,Txp]
-        n = std::max(n, mtts::align_up(w.total, 256) + mtts::align_up((size_t)B * 2 * 4, 256) +
-                            (size_t)B * Ty * (Tx > w.Txp ? Tx : w.Txp) * 4);
-    }
-    return n;
+    const WsLayout w = ws_layout(B, Tx, Ty);
+    // the DP's buffers, t_x / t_y, and the lattice: row-major [B,Tx,Ty] or transposed [B,Ty,Txp]
+    return mtts::align_up(w.total, 256) + mtts::align_up((size_t)B * 2 * 4, 256) +
+           (size_t)B * Ty * (Tx > w.Txp ? Tx : w.Txp) * 4;
 }
 
 extern "C" int mtts_prior_maximum_path(const float *mu_x, const float *y, const int64_t *x_lengths,
@@ -1609,7 +1471,7 @@ extern "C" int mtts_prior_maximum_path(const float *mu_x, const float *y, const 
     if (B == 0) return MTTS_OK;
     MTTS_CHECK_ARG(mu_x && y && x_lengths && y_lengths && C >= 1, "prior_maximum_path: null input or C < 1");
     MTTS_CHECK_ARG(B <= 65535, "prior_maximum_path: B > 65535");
-    const WsLayout w = ws_layout(B, Tx, Ty, false, !lattice_out);  // a caller lattice_out is row-major
+    const WsLayout w = ws_layout(B, Tx, Ty);
     if (!workspace || workspace_bytes < mtts_prior_maximum_path_workspace_size(B, Tx, Ty))
         return mtts::fail(MTTS_ERR_WORKSPACE, "prior_maximum_path: workspace too small");
     char *ws = static_cast<char *>(workspace);
@@ -1699,7 +1561,7 @@ extern "C" int mtts_compute_batch_alignments(int32_t *paths, float *values, cons
     if (rc) return rc;
     if (B == 0) return MTTS_OK;
     MTTS_CHECK_ARG(paths && values && t_xs && t_ys, "compute_batch_alignments: null pointer");
-    const WsLayout w = ws_layout(B, Tx, Ty, false, false);  // row-major lattice (the in-place core.pyx API)
+    const WsLayout w = ws_layout(B, Tx, Ty);  // row-major lattice (the in-place core.pyx API): no transposed copy
     if (!workspace || workspace_bytes < w.total)
         return mtts::fail(MTTS_ERR_WORKSPACE, "compute_batch_alignments: workspace too small");
     char *ws = static_cast<char *>(workspace);

@@ -111,11 +111,15 @@ def _rand_case(rng, B, Tx, Ty, ties=False):
                                    (257, 700), (300, 999), (511, 1001), (512, 512), (77, 33 * 32 + 5),
                                    (513, 600), (700, 1501), (1024, 1024), (1000, 2100), (1025, 1100),
                                    (1500, 2999), (2048, 2048), (2047, 4096), (2049, 2100), (3000, 3333),
-                                   (4095, 4095), (4096, 4200)])
+                                   (4095, 4095), (4096, 4200), (130, 1541)])
 def test_random_vs_oracle(Tx, Ty):
-    """Every DP specialisation -- the one-wave kernel (Tx <= 64) and the multi-wave one (2 / 4 / 8 waves,
-    1 / 2 / 4 / 8 rows per lane, up to Tx = 4096) --, odd Ty (scalar loads), LDS- and HBM-resident
-    backpointers, square lattices (forced diagonal), partial last 32-column chunks, and ties."""
+    """Every DP shape up to Tx = 4096 -- the one-wave kernel at 1 / 2 / 4 rows per lane (Tx <= 256) and the
+    eight-wave one at 1 / 2 / 4 / 8 rows per lane above --, each twice: compute_batch_alignments on the row-major
+    premasked lattice with the mutated lattice written (dp_out), and maximum_path(value, mask), which runs the
+    row-major value * mask kernels to Tx = 128 and the transposed lattice above.  Odd Ty (scalar loads) and
+    Ty % 4 == 0 (float4 loads), LDS- and HBM-resident backpointers in both kernels ((130, 1541): the one-wave
+    kernel's words past the 48 KiB LDS budget), square lattices (forced diagonal), partial last 32-column
+    chunks, and ties."""
     rng = np.random.default_rng(Tx * 10007 + Ty)
     for ties in (False, True):
         value, t_x, t_y = _rand_case(rng, 3, Tx, max(Ty, Tx), ties)
@@ -189,11 +193,14 @@ def test_no_host_sync_and_stream_ordering():
 
 # ---------------------------------------------------------------- fused prior lattice + MAS
 @pytest.mark.parametrize("B,C,Tx,Ty", [(4, 80, 13, 37), (3, 80, 64, 65), (2, 80, 200, 1000), (32, 80, 120, 600),
-                                       (2, 16, 1, 5), (3, 80, 300, 301)])
+                                       (2, 16, 1, 5), (3, 80, 300, 301), (2, 16, 513, 520), (2, 16, 1025, 1030),
+                                       (1, 16, 2049, 2052)])
 def test_prior_maximum_path_vs_oracle(B, C, Tx, Ty):
     """mtts_prior_maximum_path: the masked lattice is bit-identical to the numpy restatement of
     matcha_tts.py:277-282 (oracle/prior_oracle.py), the path bit-identical to the CPU oracle's
-    maximum_path on that lattice, durations == path.sum(-1), col_row == the path's row per frame."""
+    maximum_path on that lattice, durations == path.sum(-1), col_row == the path's row per frame.
+    With return_lattice the DP runs the row-major premasked kernels without dp_out: one wave to Tx = 256,
+    eight waves at 1 / 2 / 4 / 8 rows per lane above (Tx = 300 / 513 / 1025 / 2049)."""
     from matcha.utils.monotonic_align import prior_maximum_path
     from oracle import prior_oracle as PO
 
@@ -220,7 +227,7 @@ def test_prior_maximum_path_vs_oracle(B, C, Tx, Ty):
 
 
 @pytest.mark.parametrize("Tx,Ty", [(1, 1), (5, 7), (64, 64), (120, 600), (129, 301), (257, 700), (512, 4096),
-                                   (1025, 1100), (2049, 2100), (4096, 4100)])
+                                   (600, 640), (1025, 1100), (2049, 2100), (4096, 4100)])
 def test_transposed_and_row_major_lattice_agree(Tx, Ty, monkeypatch):
     """maximum_path(value, mask) with the DP on the premasked transposed lattice (default: one coalesced
     transpose, column-major loads) and on the row-major one (MTTS_MAS_TR=0: lane-per-row loads, value * mask

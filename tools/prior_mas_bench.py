@@ -1,9 +1,8 @@
 """Times the fused training alignment step (mtts_prior_maximum_path: log-prior lattice + DP + runs) and
-the mu_y gather backward (mtts_expand_rows_bwd) with HIP events, inputs resident in HBM.  The DP ring
-depth is read from MTTS_MAS_RING at first launch.  Usage: python tools/prior_mas_bench.py [--iters N]"""
+the mu_y gather backward (mtts_expand_rows_bwd) with HIP events, inputs resident in HBM.
+Usage: python tools/prior_mas_bench.py [--iters N]"""
 import argparse
 import json
-import os
 import sys
 from pathlib import Path
 
@@ -57,6 +56,5 @@ for cfg in args.configs.split(","):
     attn = out[0].double()
     ref = torch.bmm(dy.double(), attn.transpose(1, 2))
     err = (dx.double() - ref).abs().max().item()
-    print(json.dumps({"cfg": cfg, "ring": os.environ.get("MTTS_MAS_RING", "default"),
-                      "prior_maximum_path_ms": round(ms, 4), "expand_rows_bwd_ms": round(ms_bwd, 4),
+    print(json.dumps({"cfg": cfg, "prior_maximum_path_ms": round(ms, 4), "expand_rows_bwd_ms": round(ms_bwd, 4),
                       "bwd_max_abs_err": err}), flush=True)

@@ -1,8 +1,8 @@
 """Fast-iteration harness for the multi-wave MAS DP (csrc/mas.hip mas_dp_mw_kernel, transposed premasked lattice):
 extracts the kernel and its helpers from mas.hip into a small HIP file with a launcher (seconds to build instead of
-the ~20 minutes of the whole mas.hip), runs it on random lattices, checks the row starts bit for bit against the
-C oracle (oracle/mas_oracle.c, the checker) and times it; MTTS_MAS_STAMPS splits the time into forward DP and
-backtrack per utterance.
+the ~3.5 minutes of the whole mas.hip; ~7 before the sweeps' instantiations went), runs it on random lattices, checks
+the row starts bit for bit against the C oracle (oracle/mas_oracle.c, the checker) and times it; MTTS_MAS_STAMPS splits
+the time into forward DP and backtrack per utterance.
 
 build (here):   python tools/r6/mas_probe.py build            -> tools/r6/_mas_probe.so (git-ignored)
 run (GPU box):  python tools/r6/mas_probe.py run [--configs 8x512x4096,...] [--iters 20]"""
