@@ -16,6 +16,7 @@
  *   mtts_prior_maximum_path        <- matcha/models/matcha_tts.py:276-288 (log-prior lattice + maximum_path +
  *                                     the duration target), fused
  *   mtts_expand_rows_fwd / _bwd    <- matcha/models/matcha_tts.py:314-315  mu_y = attn^T @ mu_x
+ *   mtts_segment_crop_fwd / _bwd   <- matcha/models/matcha_tts.py:290-315  forward(out_size=...): random mel segment
  *   mtts_compute_batch_alignments  <- matcha/utils/monotonic_align/core.pyx:101-128   compute_batch_alignments(...)
  *                                     (bound as maximum_path_c, __init__.py:4-8)
  *   mtts_losses_fwd / _bwd         <- flow_matching.py:145-149 (CFM loss) + matcha_tts.py:319-323 (prior loss)
@@ -131,6 +132,35 @@ int mtts_expand_rows_fwd(const float *src, const int32_t *col_row, int32_t B, in
                          float *dst, void *hip_stream);
 int mtts_expand_rows_bwd(const float *dy, const int32_t *row_start, const int32_t *lengths, int32_t B, int32_t C,
                          int32_t Tx, int32_t Ty, float *dx, void *hip_stream);
+
+/*
+ * Random mel segment of the training forward (matcha_tts.py:290-315, forward(out_size=S)), fused with the
+ * alignment's consumers: per utterance b, with (t_x, t_y) = lengths[b],
+ *   cut_len = min(t_y, S), max_off = max(t_y - S, 0)   (cut_len = 0, off = 0 when t_x == 0 or t_y == 0)
+ *   off = clamp(offsets_in[b], 0, max_off)              with offsets_in (int32 [B]; clamped on the device),
+ *       = (uint64(rand_words[b]) * max_off) >> 31       otherwise (rand_words int32 [B] in [0, 2^31)): uniform on
+ *         [0, max_off) -- max_off itself is never drawn and max_off <= 1 gives 0, as the reference's
+ *         random.choice(range(0, max_offset)) (:292-295).  Integer arithmetic only: exact on the host.
+ *   y_cut[b,c,j]    = y[b,c,off+j]                    j < cut_len, else 0       float32 [B,C,S]
+ *   mu_y_cut[b,c,j] = mu_x[b,c,col_row[b,off+j]]      j < cut_len, else 0       float32 [B,C,S]
+ *   attn_cut[b,i,j] = (j < cut_len && col_row[b,off+j] == i)                    float32 [B,Tx,S], optional
+ *   mask_cut[b,j]   = j < cut_len                                               float32 [B,S]
+ *   seg[b]          = (off, cut_len)                                            int32 [B,2]
+ * y [B,C,Ty], mu_x [B,C,Tx] float32; col_row [B,Ty], lengths [B,2] as mtts_prior_maximum_path wrote them.  One of
+ * rand_words / offsets_in must be given (offsets_in wins).  One launch; 1 <= S <= Ty.
+ *
+ * bwd: d_mu_x[b,c,i] = sum of d_mu_y_cut[b,c,j] over the frames of row i inside the window.  Bit for bit what
+ * mtts_expand_rows_bwd returns for a full-length dy that holds d_mu_y_cut in [off, off+cut_len) and zeros
+ * elsewhere: lane l of 16 takes the frames row_start + l + 16k that fall in the window, then the same xor tree,
+ * per 4096-frame slab of the full-length frame axis.  Deterministic, no atomics.
+ */
+int mtts_segment_crop_fwd(const float *y, const float *mu_x, const int32_t *col_row, const int32_t *lengths,
+                          const int32_t *rand_words, const int32_t *offsets_in, int32_t B, int32_t C, int32_t Tx,
+                          int32_t Ty, int32_t S, float *y_cut, float *mu_y_cut, float *attn_cut, float *mask_cut,
+                          int32_t *seg, void *hip_stream);
+int mtts_segment_crop_bwd(const float *d_mu_y_cut, const int32_t *row_start, const int32_t *lengths,
+                          const int32_t *seg, int32_t B, int32_t C, int32_t Tx, int32_t S, float *d_mu_x,
+                          void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Log-mel features of the data path (matcha/utils/audio_process.py:32-81, MelSpectrogram.__call__)

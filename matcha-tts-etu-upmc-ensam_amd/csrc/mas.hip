@@ -1185,22 +1185,40 @@ __global__ __launch_bounds__(256) void expand_rows_fwd_kernel(const float *__res
 // loads when the rows allow), then 16 lanes per (channel, row x) sum its run from LDS.  The
 // earlier 8-channel blocks gave B*10 workgroups -- 80 at the long-form shape (B=8, Ty=4096), 940 us per
 // call on a latency-bound load phase; 2 channels give 4x the workgroups and 16-byte loads.
+//
+// kWin (mtts_segment_crop_bwd): dy is the cropped gradient [B,C,Ty = S] of the window seg[b] = (offset, cut_len)
+// of the frame axis, standing for a full-length dy that is zero outside the window.  The slabs, each lane's
+// frames (run start + l + 16k) and the xor tree stay those of the full-length sum; only the window is staged and
+// only its frames are added (the skipped terms are +0: the result is bit-identical).
 constexpr int kErC = 2;
 constexpr int kErMaxTy = 4096;
-template <bool kVec>
+template <bool kVec, bool kWin = false>
 __global__ __launch_bounds__(256) void expand_rows_bwd_kernel(const float *__restrict__ dy,
                                                               const int32_t *__restrict__ row_start,
                                                               const int32_t *__restrict__ lengths, int C, int Tx,
-                                                              int Ty, float *__restrict__ dx) {
+                                                              int Ty, float *__restrict__ dx,
+                                                              const int32_t *__restrict__ seg = nullptr) {
     __shared__ __attribute__((aligned(16))) float sdy[kErC * kErMaxTy];
     const int b = blockIdx.y, c0 = blockIdx.x * kErC;
     const int nc = min(kErC, C - c0);
     const int t_x = lengths[2 * b], t_y = lengths[2 * b + 1];
     const int32_t *rs = row_start + (size_t)b * Tx;
-    for (int ty0 = 0; ty0 < Ty; ty0 += kErMaxTy) {  // frame slabs (one slab for Ty <= 4096)
-        const int tn = min(kErMaxTy, Ty - ty0);
+    int w0 = 0, w1 = 0;  // kWin: the window's frames [w0, w1)
+    if (kWin) {
+        w0 = max(seg[2 * b], 0);
+        w1 = w0 + min(max(seg[2 * b + 1], 0), Ty);
+    }
+    const int ext = kWin ? max(t_y, 1) : Ty;  // the full-length frame axis (kWin: no row reaches past t_y)
+    for (int ty0 = 0; ty0 < ext; ty0 += kErMaxTy) {  // frame slabs (one slab for Ty <= 4096)
+        const int tn = min(kErMaxTy, ext - ty0);
         __syncthreads();
-        if (kVec) {  // Ty % 4 == 0, dy 16-byte aligned: every slab row starts 16-byte aligned
+        if (kWin) {  // the window's part of this slab (source rows start at any alignment: scalar loads)
+            const int a = max(w0, ty0), n = min(w1, ty0 + tn) - a;
+            for (int e = threadIdx.x; e < nc * n; e += 256) {
+                const int c = e / n, i = e - c * n;
+                sdy[c * kErMaxTy + (a - ty0) + i] = dy[((size_t)b * C + c0 + c) * Ty + (a - w0) + i];
+            }
+        } else if (kVec) {  // Ty % 4 == 0, dy 16-byte aligned: every slab row starts 16-byte aligned
             const int tn4 = tn >> 2;
             for (int e = threadIdx.x; e < nc * tn4; e += 256) {
                 const int c = e / tn4, q = e - c * tn4;
@@ -1228,7 +1246,13 @@ __global__ __launch_bounds__(256) void expand_rows_bwd_kernel(const float *__res
                 hi = min(en, ty0 + tn) - ty0;
             }
             float acc = 0.f;
-            for (int yy = lo + l16; yy < hi; yy += 16) acc += sdy[c * kErMaxTy + yy];
+            int yy = lo + l16;
+            if (kWin) {  // this lane's first frame inside the window; the run ends where the window does
+                const int wl = w0 - ty0;
+                if (yy < wl) yy += ((wl - yy + 15) >> 4) << 4;
+                hi = min(hi, w1 - ty0);
+            }
+            for (; yy < hi; yy += 16) acc += sdy[c * kErMaxTy + yy];
             acc += __shfl_xor(acc, 8, 16);
             acc += __shfl_xor(acc, 4, 16);
             acc += __shfl_xor(acc, 2, 16);
@@ -1239,6 +1263,85 @@ __global__ __launch_bounds__(256) void expand_rows_bwd_kernel(const float *__res
             }
         }
     }
+}
+
+// forward(out_size = S) of the reference (matcha_tts.py:290-315): a random window of S frames per utterance, cut
+// from y and from the alignment, fused with the mu_y gather.  The offset is integer arithmetic on one 31-bit word
+// per utterance (include/mtts.h), so every block recomputes it instead of reading it from an earlier launch.
+__device__ __forceinline__ void segment_window(const int32_t *__restrict__ lengths,
+                                               const int32_t *__restrict__ rand_words,
+                                               const int32_t *__restrict__ offsets_in, int b, int Ty, int S, int &off,
+                                               int &cut) {
+    const int t_x = lengths[2 * b];
+    const int t_y = t_x >= 1 ? min(max(lengths[2 * b + 1], 0), Ty) : 0;
+    cut = min(t_y, S);
+    const int max_off = max(t_y - S, 0);
+    if (offsets_in)
+        off = min(max(offsets_in[b], 0), max_off);
+    else  // uniform on [0, max_off): never max_off itself, 0 for max_off <= 1 (random.choice(range(0, max_off)))
+        off = (int)(((uint64_t)((uint32_t)rand_words[b] & 0x7fffffffu) * (uint64_t)max_off) >> 31);
+}
+
+template <bool kVec>
+__device__ __forceinline__ void segment_store4(float *__restrict__ row, int j0, int S, const float (&v)[4]) {
+    if (kVec) {  // S % 4 == 0 and a 16-byte aligned base: every row's quads are 16-byte aligned
+        *reinterpret_cast<float4 *>(row + j0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (j0 + i < S) row[j0 + i] = v[i];
+    }
+}
+
+// one thread per 4 consecutive frames of one output row; the rows of an utterance are the C channels (y_cut and
+// mu_y_cut together), then the Tx rows of attn_cut (when asked for), then the mask.  The source rows y + off start
+// at any alignment, so the loads are scalar (the tensors are B*C*S small); the stores are 16 bytes.
+template <bool kVec>
+__global__ __launch_bounds__(256) void segment_crop_fwd_kernel(
+    const float *__restrict__ y, const float *__restrict__ mu_x, const int32_t *__restrict__ col_row,
+    const int32_t *__restrict__ lengths, const int32_t *__restrict__ rand_words,
+    const int32_t *__restrict__ offsets_in, int C, int Tx, int Ty, int S, float *__restrict__ y_cut,
+    float *__restrict__ mu_y_cut, float *__restrict__ attn_cut, float *__restrict__ mask_cut,
+    int32_t *__restrict__ seg) {
+    const int b = blockIdx.y;
+    int off, cut;
+    segment_window(lengths, rand_words, offsets_in, b, Ty, S, off, cut);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        seg[2 * b] = off;
+        seg[2 * b + 1] = cut;
+    }
+    const int Q = (S + 3) >> 2;
+    const int R = C + (attn_cut ? Tx : 0) + 1;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)R * Q) return;
+    const int r = (int)(idx / Q), j0 = 4 * (int)(idx - (size_t)r * Q);
+    float v[4];
+    if (r == R - 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = j0 + i < cut ? 1.f : 0.f;
+        segment_store4<kVec>(mask_cut + (size_t)b * S, j0, S, v);
+        return;
+    }
+    int row[4];  // the text row of each frame (off + j < off + cut <= t_y <= Ty); -2 past the window
+#pragma unroll
+    for (int i = 0; i < 4; ++i) row[i] = j0 + i < cut ? col_row[(size_t)b * Ty + off + j0 + i] : -2;
+    if (r >= C) {
+        const int x = r - C;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = row[i] == x ? 1.f : 0.f;
+        segment_store4<kVec>(attn_cut + ((size_t)b * Tx + x) * S, j0, S, v);
+        return;
+    }
+    const float *ys = y + ((size_t)b * C + r) * Ty + off;
+    const float *ms = mu_x + ((size_t)b * C + r) * Tx;
+    float m[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[i] = j0 + i < cut ? ys[j0 + i] : 0.f;
+        m[i] = (row[i] >= 0 && row[i] < Tx) ? ms[row[i]] : 0.f;
+    }
+    segment_store4<kVec>(y_cut + ((size_t)b * C + r) * S, j0, S, v);
+    segment_store4<kVec>(mu_y_cut + ((size_t)b * C + r) * S, j0, S, m);
 }
 
 struct WsLayout {
@@ -1550,6 +1653,44 @@ extern "C" int mtts_expand_rows_bwd(const float *dy, const int32_t *row_start, c
     else
         hipLaunchKernelGGL(expand_rows_bwd_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(hip_stream), dy,
                            row_start, lengths, C, Tx, Ty, dx);
+    return mtts::check_launch("expand_rows_bwd_kernel");
+}
+
+extern "C" int mtts_segment_crop_fwd(const float *y, const float *mu_x, const int32_t *col_row,
+                                     const int32_t *lengths, const int32_t *rand_words, const int32_t *offsets_in,
+                                     int32_t B, int32_t C, int32_t Tx, int32_t Ty, int32_t S, float *y_cut,
+                                     float *mu_y_cut, float *attn_cut, float *mask_cut, int32_t *seg,
+                                     void *hip_stream) {
+    MTTS_CHECK_ARG(y && mu_x && col_row && lengths && y_cut && mu_y_cut && mask_cut && seg && B >= 0 && C >= 0 &&
+                       Tx >= 1 && Ty >= 1 && B <= 65535,
+                   "segment_crop_fwd: bad args");
+    MTTS_CHECK_ARG(rand_words || offsets_in, "segment_crop_fwd: neither rand_words nor offsets_in");
+    MTTS_CHECK_ARG(S >= 1 && S <= Ty, "segment_crop_fwd: out_size outside [1, Ty]");
+    if (B == 0) return MTTS_OK;
+    const size_t rows = (size_t)C + (attn_cut ? Tx : 0) + 1;
+    dim3 grid((unsigned)((rows * ((S + 3) / 4) + 255) / 256), B);
+    const bool vec = (S % 4 == 0) && (((uintptr_t)y_cut | (uintptr_t)mu_y_cut | (uintptr_t)attn_cut |
+                                       (uintptr_t)mask_cut) % 16 == 0);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (vec)
+        hipLaunchKernelGGL(segment_crop_fwd_kernel<true>, grid, dim3(256), 0, st, y, mu_x, col_row, lengths,
+                           rand_words, offsets_in, C, Tx, Ty, S, y_cut, mu_y_cut, attn_cut, mask_cut, seg);
+    else
+        hipLaunchKernelGGL(segment_crop_fwd_kernel<false>, grid, dim3(256), 0, st, y, mu_x, col_row, lengths,
+                           rand_words, offsets_in, C, Tx, Ty, S, y_cut, mu_y_cut, attn_cut, mask_cut, seg);
+    return mtts::check_launch("segment_crop_fwd_kernel");
+}
+
+extern "C" int mtts_segment_crop_bwd(const float *d_mu_y_cut, const int32_t *row_start, const int32_t *lengths,
+                                     const int32_t *seg, int32_t B, int32_t C, int32_t Tx, int32_t S,
+                                     float *d_mu_x, void *hip_stream) {
+    MTTS_CHECK_ARG(d_mu_y_cut && row_start && lengths && seg && d_mu_x && B >= 0 && C >= 0 && Tx >= 1 && S >= 1 &&
+                       B <= 65535,
+                   "segment_crop_bwd: bad args");
+    if ((size_t)B * C * Tx == 0) return MTTS_OK;
+    dim3 grid((unsigned)((C + kErC - 1) / kErC), B);
+    hipLaunchKernelGGL((expand_rows_bwd_kernel<false, true>), grid, dim3(256), 0,
+                       static_cast<hipStream_t>(hip_stream), d_mu_y_cut, row_start, lengths, C, Tx, S, d_mu_x, seg);
     return mtts::check_launch("expand_rows_bwd_kernel");
 }
 

@@ -45,6 +45,7 @@ class MatchaTTS(BaseLightningClass):
     # near-tie flipped), "fp32" (exact fp32 MFMA forward and backward)
     # None: the ambient default (_ops.parity_policy sets "fp32fwd", otherwise "bf16")
     encoder_precision = None
+    last_seg = None  # forward(out_size=...) on the device: the windows of the last forward (see forward)
 
     @property
     def encoder_fp32(self) -> bool:
@@ -121,9 +122,20 @@ class MatchaTTS(BaseLightningClass):
             return y_square - y_mu_double + mu_square + const
 
     def forward(self, x, x_lengths, y, y_lengths, out_size=None, cond=None, durations=None, *, t=None, z=None,
-                segments=1):
+                segments=1, out_offset=None):
         """Returns (dur_loss, prior_loss, diff_loss, attn) -- matcha_tts.py:247-325.  ``t``/``z``
-        (keyword-only) inject the CFM randomness for parity tests.  ``segments`` = n > 1 (keyword-only, the
+        (keyword-only) inject the CFM randomness for parity tests.
+
+        ``out_size`` = S (:290-312): after the alignment every utterance is cut to a random window of S mel
+        frames; the decoder, the CFM loss and the prior loss run on the window (``z`` is then [B, n_feats, S]),
+        the duration loss on the whole utterance, and ``attn`` is the window [B, Tx, S].  On CUDA with the GPU
+        alignment the crop is one HIP launch each way (monotonic_align.segment_crop): no host sync, windows
+        drawn on the device from torch's generator (a replayed graph draws fresh ones), ``out_offset``
+        (keyword-only, int tensor [B], clamped on the device to [0, max(t_y - S, 0)]) injects them.  ``y_mask``
+        has length S there; the reference's sequence_mask(y_cut_lengths) (:308) has length max(cut_len), which
+        is S whenever any utterance reaches S frames -- and the reference cannot run otherwise.  CPU tensors,
+        use_precomputed_durations and MTTS_SEGMENT_HOST=1 keep the reference's host-side crop (Python's
+        ``random``, a device->host copy, the dense attn matmul).  ``segments`` = n > 1 (keyword-only, the
         Trainer's merged micro-batches): the batch is n equal micro-batches stacked along dim 0 and each loss
         is returned per micro-batch (a [n] tensor, every one normalised by its own micro-batch's lengths, as n
         separate forwards would) -- every other op of the model is per utterance."""
@@ -167,9 +179,12 @@ class MatchaTTS(BaseLightningClass):
         else:
             # :276-288 fused on the GPU: lattice (log_prior) * attn_mask -> maximum_path -> sum(attn, -1),
             # with the attention mask taken from the lengths (never materialised)
+            # out_size on the device: the window is cut from the runs, the dense [B,Tx,Ty] path is never written
+            crop_dev = out_size is not None and x.is_cuda and os.environ.get("MTTS_SEGMENT_HOST", "0") != "1"
             with torch.no_grad():
                 attn, dur, col_row, row_start, lens = monotonic_align.prior_maximum_path(mu_x, y, x_lengths,
-                                                                                          y_lengths)
+                                                                                          y_lengths,
+                                                                                          dense=not crop_dev)
             runs = (col_row, row_start, lens)
         # logw_ = log(1e-8 + dur) * x_mask ; duration_loss(logw, logw_, x_lengths)  (:287-288, model.py:117-135)
         # as one HIP launch each way
@@ -181,7 +196,16 @@ class MatchaTTS(BaseLightningClass):
                                                           x_lengths[i * bs:(i + 1) * bs]) for i in range(segments)])
         else:
             dur_loss = O.duration_loss_fused(logw, dur, x_lengths)
-        if out_size is not None:  # :290-312 (host-side random crop, as the reference)
+        mu_y = None
+        if out_size is not None and runs is not None and attn is None:
+            # :290-315 in one launch: y_cut, mu_y_cut = the window of attn^T @ mu_x, attn_cut and the mask
+            # last_seg: int32 [B, 2] = (offset, cut_len) of this forward's windows (inside a captured step, the
+            # tensor every replay rewrites)
+            y, mu_y, attn, y_mask, self.last_seg = monotonic_align.segment_crop(y, mu_x, *runs, out_size,
+                                                                               offsets=out_offset)
+        elif out_size is not None:  # :290-312 (host-side random crop, as the reference)
+            if out_offset is not None:
+                raise ValueError("out_offset injects the device crop's windows; the host-side crop draws its own")
             max_offset = (y_lengths - out_size).clamp(0)
             offset_ranges = list(zip([0] * max_offset.shape[0], max_offset.cpu().numpy()))
             out_offset = torch.LongTensor([random.choice(range(s, e)) if e > s else 0
@@ -198,7 +222,9 @@ class MatchaTTS(BaseLightningClass):
             y_mask = sequence_mask(y_cut_lengths).unsqueeze(1).to(y_mask)
             attn, y = attn_cut, y_cut
             runs = None
-        if runs is not None:  # attn^T @ mu_x on the one-hot attn == a gather (bitwise), segment-sum backward
+        if mu_y is not None:  # the device crop gathered its window of mu_y already
+            pass
+        elif runs is not None:  # attn^T @ mu_x on the one-hot attn == a gather (bitwise), segment-sum backward
             mu_y = monotonic_align.expand_rows(mu_x, *runs)
         else:
             mu_y = torch.matmul(attn.squeeze(1).transpose(1, 2), mu_x.transpose(1, 2)).transpose(1, 2)

@@ -36,7 +36,8 @@ shapes on its own (tested over gloo; not yet run with the in-graph RCCL transpor
 
 Synthetic LJSpeech-shaped batches: token ids ~ U{1..149}, lengths ~ U[0.7 max, max]
 with element 0 = max, mels ~ N(0, 1) zeroed past the length.  A batch dict may carry "t" [B, 1, 1] and
-"z" [B, n_feats, Ty]: the CFM randomness injected for parity tests (MatchaTTS.forward's keywords).
+"z" [B, n_feats, Ty]: the CFM randomness injected for parity tests (MatchaTTS.forward's keywords); with
+TrainConfig.out_size = S, "z" is [B, n_feats, S] and "out_offset" [B] injects the segment windows.
 """
 from __future__ import annotations
 
@@ -219,6 +220,12 @@ class TrainConfig:
     # statistics per utterance and padded length), so only the weight-gradient reductions' rounding differs.
     # Micro-batches of different padded shapes take the stashed fresh-gradient path (_fwd_bwd_stash)
     merge_micro_batches: bool = True
+    # train on a random window of out_size mel frames per utterance (MatchaTTS.forward(out_size=...), the
+    # reference's matcha_tts.py:290-312): the decoder and the CFM / prior losses see the window, the alignment
+    # and the duration loss the whole utterance.  The windows are drawn on the device inside the step, so a
+    # captured step replays with fresh ones; a batch's "out_offset" (int [B]) injects them, "z" is then
+    # [B, n_feats, out_size].  None: whole utterances
+    out_size: int | None = None
 
 
 class Trainer:
@@ -375,7 +382,10 @@ class Trainer:
             first = deferred_grad_sums(True) if (i == 0 and getattr(self, "_defer_first", False)) \
                 else contextlib.nullcontext()
             with ctx, first:
-                inject = {k: batch[k] for k in ("t", "z") if k in batch}  # parity tests' CFM randomness
+                # parity tests' CFM randomness and segment windows
+                inject = {k: batch[k] for k in ("t", "z", "out_offset") if k in batch}
+                if self.cfg.out_size is not None:
+                    inject["out_size"] = self.cfg.out_size
                 seg = batch.get("_segments", 1)
                 if seg > 1:  # merged micro-batches: per-micro-batch losses ([seg] tensors)
                     inject["segments"] = seg
@@ -612,7 +622,7 @@ class Trainer:
                 b["x"] = torch.nn.functional.pad(b["x"], (0, tx - b["x"].shape[1]))
             if b["y"].shape[2] < ty:
                 b["y"] = torch.nn.functional.pad(b["y"], (0, ty - b["y"].shape[2]))
-                if "z" in b:
+                if "z" in b and self.cfg.out_size is None:  # with out_size, z is [B, n_feats, out_size]
                     b["z"] = torch.nn.functional.pad(b["z"], (0, ty - b["z"].shape[2]))
             out.append(b)
         return out

@@ -105,7 +105,7 @@ compute_batch_alignments = maximum_path_c
 
 
 def prior_maximum_path(mu_x: torch.Tensor, y: torch.Tensor, x_lengths: torch.Tensor, y_lengths: torch.Tensor, *,
-                       return_lattice: bool = False):
+                       return_lattice: bool = False, dense: bool = True):
     """The training forward's alignment step fused (matcha_tts.py:276-288, MatchaTTS.forward):
     log-prior lattice from mu_x [B,C,Tx] and y [B,C,Ty] (fp32), masked by the length masks, Viterbi
     max path, and the duration target -- one lattice write to HBM instead of two bmm's, their
@@ -114,7 +114,9 @@ def prior_maximum_path(mu_x: torch.Tensor, y: torch.Tensor, x_lengths: torch.Ten
 
     Returns (attn [B,Tx,Ty] fp32, dur [B,Tx] fp32 = attn.sum(-1), col_row [B,Ty] int32 = text row of
     each frame (-1 past t_y), row_start [B,Tx] int32, lengths [B,2] int32) and, with
-    ``return_lattice``, the masked fp32 lattice [B,Tx,Ty] the DP ran on.  No gradient."""
+    ``return_lattice``, the masked fp32 lattice [B,Tx,Ty] the DP ran on.  No gradient.
+    ``dense=False`` skips the dense path (attn is None: the C entry's optional ``path``, one launch and a
+    [B,Tx,Ty] write less) for consumers that read the runs only (segment_crop); nothing else changes."""
     N.require_device(mu_x, y, x_lengths, y_lengths)
     if mu_x.dim() != 3 or y.dim() != 3 or mu_x.shape[:2] != y.shape[:2]:
         raise ValueError(f"prior_maximum_path expects mu_x [B,C,Tx] and y [B,C,Ty], got {tuple(mu_x.shape)}, "
@@ -127,7 +129,7 @@ def prior_maximum_path(mu_x: torch.Tensor, y: torch.Tensor, x_lengths: torch.Ten
     _check_tx(Tx)
     Ty = y.shape[2]
     dev = mu_x.device
-    attn = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev)
+    attn = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev) if dense else None
     dur = torch.empty((B, Tx), dtype=torch.float32, device=dev)
     col_row = torch.empty((B, Ty), dtype=torch.int32, device=dev)
     row_start = torch.empty((B, Tx), dtype=torch.int32, device=dev)
@@ -176,3 +178,90 @@ def expand_rows(mu_x: torch.Tensor, col_row: torch.Tensor, row_start: torch.Tens
     equal to the bmm on the one-hot attn: every other term is 0 * finite)."""
     N.require_device(mu_x, col_row, row_start, lengths)
     return _ExpandRows.apply(mu_x, col_row, row_start, lengths)
+
+
+def segment_offset_host(word: int, t_y: int, out_size: int) -> tuple[int, int]:
+    """The device's window rule restated in Python integers (include/mtts.h, mtts_segment_crop_fwd): for a
+    31-bit random word, (offset, cut_len) of an utterance of t_y frames cropped to out_size.  The offset is
+    uniform on [0, max_off) with max_off = max(t_y - out_size, 0): max_off itself is never drawn and
+    max_off <= 1 gives 0, as the reference's random.choice(range(0, max_offset)) (matcha_tts.py:292-295)."""
+    max_off = max(int(t_y) - int(out_size), 0)
+    return ((int(word) & 0x7FFFFFFF) * max_off) >> 31, min(max(int(t_y), 0), int(out_size))
+
+
+class _SegmentCrop(torch.autograd.Function):
+    """mtts_segment_crop_fwd / _bwd: the window of y, of mu_y = attn^T @ mu_x and of attn in one launch; the
+    backward sums each text row's frames inside the window in expand_rows' order (bitwise equal to its backward
+    on the zero-padded full-length gradient)."""
+
+    @staticmethod
+    def forward(ctx, mu_x, y, col_row, row_start, lengths, out_size, offsets, words, want_attn):
+        ctx.in_dtype = mu_x.dtype
+        mu_x = mu_x.to(torch.float32).contiguous()
+        B, C, Tx = mu_x.shape
+        Ty, S, dev = y.shape[2], int(out_size), mu_x.device
+        y_cut = torch.empty((B, C, S), dtype=torch.float32, device=dev)
+        mu_y_cut = torch.empty((B, C, S), dtype=torch.float32, device=dev)
+        attn_cut = torch.empty((B, Tx, S), dtype=torch.float32, device=dev) if want_attn else None
+        mask = torch.empty((B, 1, S), dtype=torch.float32, device=dev)
+        seg = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            N.check(N.lib().mtts_segment_crop_fwd(
+                N.ptr(y), N.ptr(mu_x), N.ptr(col_row), N.ptr(lengths), N.ptr(words), N.ptr(offsets), B, C, Tx, Ty, S,
+                N.ptr(y_cut), N.ptr(mu_y_cut), N.ptr(attn_cut), N.ptr(mask), N.ptr(seg), N.stream_handle(dev)),
+                "mtts_segment_crop_fwd")
+        ctx.save_for_backward(row_start, lengths, seg)
+        ctx.shape = (B, C, Tx, S)
+        ctx.mark_non_differentiable(*(t for t in (y_cut, attn_cut, mask, seg) if t is not None))
+        return y_cut, mu_y_cut, attn_cut, mask, seg
+
+    @staticmethod
+    def backward(ctx, _dy, d_mu_y, _dattn, _dmask, _dseg):
+        row_start, lengths, seg = ctx.saved_tensors
+        B, C, Tx, S = ctx.shape
+        d_mu_y = d_mu_y.to(torch.float32).contiguous()
+        dx = torch.empty((B, C, Tx), dtype=torch.float32, device=d_mu_y.device)
+        with torch.cuda.device(d_mu_y.device):
+            N.check(N.lib().mtts_segment_crop_bwd(N.ptr(d_mu_y), N.ptr(row_start), N.ptr(lengths), N.ptr(seg), B, C, Tx,
+                                                  S, N.ptr(dx), N.stream_handle(d_mu_y.device)),
+                    "mtts_segment_crop_bwd")
+        return (dx.to(ctx.in_dtype),) + (None,) * 8
+
+
+def segment_crop(y: torch.Tensor, mu_x: torch.Tensor, col_row: torch.Tensor, row_start: torch.Tensor,
+                 lengths: torch.Tensor, out_size: int, *, offsets: torch.Tensor | None = None,
+                 words: torch.Tensor | None = None, want_attn: bool = True):
+    """The reference's random mel segment (matcha_tts.py:290-315, forward(out_size=...)) on the device, for the
+    alignment prior_maximum_path returned: every utterance is cut to a window of ``out_size`` frames.
+
+    y [B,C,Ty], mu_x [B,C,Tx] -> (y_cut [B,C,S], mu_y_cut [B,C,S] = the window of attn^T @ mu_x, attn_cut
+    [B,Tx,S] (None with ``want_attn=False``), y_mask [B,1,S], seg int32 [B,2] = (offset, cut_len)), zeros past
+    cut_len = min(t_y, S).  The gradient goes to mu_x only; y is data.
+    ``offsets`` (int tensor [B]) injects the windows, clamped on the device to [0, max(t_y - S, 0)].  Otherwise
+    one 31-bit word per utterance is drawn ON THE DEVICE from torch's generator (no host sync; a replayed HIP
+    graph draws fresh windows) and mapped by segment_offset_host's rule; ``words`` (int32 [B], tests) gives
+    the words instead."""
+    N.require_device(y, mu_x, col_row, row_start, lengths, offsets, words)
+    if mu_x.dim() != 3 or y.dim() != 3 or mu_x.shape[:2] != y.shape[:2]:
+        raise ValueError(f"segment_crop expects y [B,C,Ty] and mu_x [B,C,Tx], got {tuple(y.shape)}, "
+                         f"{tuple(mu_x.shape)}")
+    B, Ty = y.shape[0], y.shape[2]
+    if not 1 <= int(out_size) <= Ty:
+        raise ValueError(f"segment_crop: out_size {out_size} outside [1, {Ty}] (the padded mel length)")
+    if tuple(col_row.shape) != (B, Ty) or tuple(row_start.shape) != (B, mu_x.shape[2]) or \
+            tuple(lengths.shape) != (B, 2):
+        raise ValueError("segment_crop: col_row / row_start / lengths are not this batch's alignment")
+    y = y.detach().to(torch.float32).contiguous()
+    if offsets is not None:
+        if tuple(offsets.shape) != (B,):
+            raise ValueError(f"segment_crop: offsets must be [B] = [{B}], got {tuple(offsets.shape)}")
+        offsets = offsets.detach().to(torch.int32).contiguous()
+        words = None
+    elif words is not None:
+        if tuple(words.shape) != (B,) or words.dtype != torch.int32:
+            raise ValueError(f"segment_crop: words must be int32 [B] = [{B}]")
+        words = words.contiguous()
+    else:
+        words = torch.randint(0, 2 ** 31 - 1, (B,), device=y.device, dtype=torch.int32)
+    return _SegmentCrop.apply(mu_x, y, col_row.contiguous(), row_start.contiguous(), lengths.contiguous(),
+                              int(out_size), offsets, words, want_attn)
