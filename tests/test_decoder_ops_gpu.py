@@ -125,11 +125,18 @@ def test_ff_tm(prec, M, C):
     _run(lambda x, w1, b1, w2, b2, r: ff_tm(x, w1, b1, w2, b2, residual=r), ref, [x, w1, b1, w2, b2, r], prec)
 
 
-def test_dropout_epilogues_consistent():
+def test_dropout_epilogues_consistent(monkeypatch):
     """Train-mode dropout: about p of the outputs dropped, survivors scaled 1/(1-p), and the backward
-    regenerates the same mask (checked against an explicit-mask torch computation)."""
+    regenerates the same mask (checked against an explicit-mask torch computation; for the FeedForward, whose
+    mask is hidden behind the second Linear, the mask recomputed on the host from the recorded seed)."""
+    import dropout_ref as DR
+    import numpy as np
+
+    from matcha.models.components import _ops as O
     from matcha.models.components._ops import ff_tm, linear_tm
 
+    seeds, new_seed = [], O._new_seed
+    monkeypatch.setattr(O, "_new_seed", lambda device: seeds.append(new_seed(device)) or seeds[-1])
     torch.manual_seed(1)
     M, K, Nn, p = 2048, 256, 256, 0.25
     x = torch.randn(M, K, device=DEV, requires_grad=True)
@@ -150,10 +157,16 @@ def test_dropout_epilogues_consistent():
     xx = torch.randn(M, K, device=DEV, requires_grad=True)
     y2 = ff_tm(xx, w1, None, w2, None, dropout_p=p)
     (y2 * g).sum().backward()
-    h = F.gelu(F.linear(xx.detach(), w1.detach()))
-    # recover the mask from a second forward with the same seed is not possible; check statistics
-    assert torch.isfinite(xx.grad).all() and torch.isfinite(w1.grad).all()
-    assert (y2 - F.linear(h, w2.detach())).abs().mean() > 0  # dropout did something
+    assert len(seeds) == 2  # linear_tm's, then ff_tm's
+    drop = torch.from_numpy(DR.keep_mask(seeds[1], np.arange(M), np.arange(4 * K), p)).to(DEV).double()
+    drop = drop * float(np.float32(DR.keep_scale(p)))
+    xr, w1r, w2r = (t.detach().double().requires_grad_(True) for t in (xx, w1, w2))
+    y2r = F.linear(F.gelu(F.linear(xr, w1r)) * drop, w2r)
+    (y2r * g.double()).sum().backward()
+    ftol, gtol = TOL["fp32"]
+    assert rel(y2, y2r) < ftol, rel(y2, y2r)
+    for got, want in ((xx.grad, xr.grad), (w1.grad, w1r.grad), (w2.grad, w2r.grad)):
+        assert rel(got, want) < gtol, (tuple(want.shape), rel(got, want))
 
 
 @pytest.mark.parametrize("B,T,C,G,masked,add", [(2, 37, 32, 8, True, True), (3, 600, 256, 8, True, True),
