@@ -122,6 +122,17 @@ size_t mtts_conv_gemm_workspace_size(const mtts_conv_gemm_args *args, int32_t pr
                                      int32_t splits);
 int mtts_conv_gemm_ws(const mtts_conv_gemm_args *args, int32_t precision, int32_t tile_cfg, int32_t splits,
                       void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Read-only plan of the same (args, precision, tile_cfg, splits): host arithmetic, no HIP call.  out[0] = the schedule
+ * id that runs, out[1] = its K splits (given the workspace mtts_conv_gemm_workspace_size asks for), and for an LDS-DMA
+ * schedule out[2] = workgroups (tiles x splits), out[3] = resident workgroups per CU, out[4] = rounds =
+ * ceil(workgroups / (256 CUs x resident)), out[5] = fill = workgroups / (rounds x 256 x resident) in per mille
+ * (zeros for the other schedules). */
+int mtts_conv_gemm_plan(const mtts_conv_gemm_args *args, int32_t precision, int32_t tile_cfg, int32_t splits,
+                        int32_t out[6]);
+/* Tests: out[0] = the schedule table's resident workgroups per CU of LDS-DMA schedule `schedule` (MTTS_GEMM_GLDS + i)
+ * for an operand kind (0 fp32 A, 1 bf16 A, 2 / 3 the same with split weights, 4 three planes), out[1] = the runtime's
+ * hipOccupancyMaxActiveBlocksPerMultiprocessor for that kernel (lean: its scalar-addressed variant). */
+int mtts_conv_gemm_glds_occupancy(int32_t schedule, int32_t kind, int32_t lean, int32_t out[2]);
 
 /*
  * Weight gradient of the same implicit GEMM:

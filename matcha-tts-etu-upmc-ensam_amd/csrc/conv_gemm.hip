@@ -1000,17 +1000,69 @@ static void launch_by_id(int id, const mtts_conv_gemm_args &p, int M, hipStream_
 //  * erf-GELU / GELU' epilogues (the FFN's 1024-wide projection and its dgrad) are epilogue-bound:
 //    the small register-staged 32 x 128 tiles (config 7) keep 3 workgroups per CU so one
 //    workgroup's epilogue overlaps another's main loop (75 vs 88 us at 19200 x 1024 x 256);
-//  * the LDS-DMA 128 x 256 kernel (8 waves of 64 x 64, 2 stages) when ITS tiles fill the chip in one
-//    round and K >= 512 (the 19200-row N = 256 convs / FFN down-projection: 26.9 vs 29.8 us -- W is
-//    re-streamed by half as many row tiles);
-//  * the LDS-DMA 64 x 256 kernel (3 stages) wins when its tiles fill the chip in ONE round
-//    (128..256 tiles, K >= 768: the half-resolution decoder GEMMs, 17.4 vs 19.0 us) -- at 300 tiles
-//    the second round's tail makes it lose to config 12;
+//  * K >= 768 from half a round of 64 x 256 tiles up: the LDS-DMA kernels, the schedule by rounds
+//    (pick_glds_rounds; a 128 x 256 tile won its isolated sweep on the 19200-row GEMMs, 26.9 vs 29.8 us, lost
+//    0.33 ms in the step, and is gone);
 //  * long reductions on grids far below the CU count (the text encoder's 3840 x 192 x 2304 conv)
 //    split K four ways on that kernel (22 vs 29 us);
 //  * everything else: 32 x 128 register tiles, 64-wide K steps two in flight (config 12) from
 //    K >= 384, 32-wide (config 7) below.  fp32 (parity mode) uses config 7.
 static int glds_tiles(const mtts_conv_gemm_args &p, int M) { return ((M + 63) / 64) * ((p.N + 255) / 256); }
+
+// How an LDS-DMA schedule covers the chip: its workgroups (tiles x K splits) against the slots the chip has at
+// once, 256 CUs x the resident workgroups per CU of the table beside kGlds[] (conv_gemm_glds.hip).
+struct GldsRounds {
+    int tiles, resident, rounds, fill_pm;  // fill = tiles / (rounds x slots), per mille
+    double us;                             // modelled time
+};
+// Model: every round costs a fixed part (launch ramp, prologue fill, epilogue) and every CU streams the stage
+// images of its workgroups through the per-CU LDS-DMA fill ceiling, which the resident workgroups share:
+//   us = rounds x kGldsFixedUs + ceil(tiles / 256) x K steps x stage bytes / kGldsFillBps.
+// With every round full, ceil(tiles / 256) = rounds x resident; a partial round counts the workgroups a CU really
+// gets (240 tiles of a two-resident schedule: one per CU).  Constants: a tile carries 3-4 us outside its K loop
+// (per-wave timelines, profiles/r06/glds_timeline/); the timelines put the fill at 75-95 GB/s per CU
+// inside the K loop, the isolated timings of all six pickable schedules on the decoder shapes (profiles/r07/
+// sweep_step.json: 32 shape x kind cases) fit 65 GB/s end to end (mean error 14 %), which is the figure used.
+// The model reproduces the fastest measured schedule on all 24 cases with a bf16 A or split weights.
+constexpr double kGldsFixedUs = 3.5, kGldsFillBps = 65e9;
+static GldsRounds glds_rounds(const mtts_conv_gemm_args &p, int M, int id, int splits) {
+    const mtts::GldsInfo g = mtts::conv_gemm_glds_info(id, p);
+    GldsRounds r = {};
+    if (g.resident < 1) return r;
+    const int nk = (p.K + 63) / 64, ksteps = splits > 1 ? (nk + splits - 1) / splits : nk;
+    const int S = splits > 1 ? (nk + ksteps - 1) / ksteps : 1;
+    const int slots = 256 * g.resident;
+    r.tiles = ((M + g.bm - 1) / g.bm) * ((p.N + g.bn - 1) / g.bn) * S;
+    r.resident = g.resident;
+    r.rounds = (r.tiles + slots - 1) / slots;
+    r.fill_pm = (int)((1000ll * r.tiles) / ((long long)r.rounds * slots));
+    r.us = r.rounds * kGldsFixedUs + (double)((r.tiles + 255) / 256) * ksteps * g.stage_bytes / kGldsFillBps * 1e6;
+    return r;
+}
+
+// The LDS-DMA schedule with the lowest modelled time among the pickable ones that have an instantiation of their
+// own for p's operand kind (whole-tap K steps: the scalar-addressed loop); on a tie the first listed, the 160-row
+// tiles first.  Exceptions, where the isolated measurement on a step shape contradicts the model's order:
+//  * fp32 A, one weight plane, more than one round of 64 x 256 tiles (the 19200-row dgrads): the model ties 41 / 42 /
+//    46 at 48 KiB per stage and puts the 64 x 64 two-stage 45 (three resident, 24 KiB) 20 % behind; measured 45 wins:
+//    19200 x 256 x 768 23.5 us vs 24.7 (46), 26.8 (41), 27.0 (42); K = 1536: 36.7 vs 43.6, 48.1, 42.2; K = 512: 18.5
+//    vs 19.8, 21.1, 21.6 -- the rule the round-2 sweep found (profiles/r02/gemm_lean), kept.
+// Checked and NOT an exception: the backward's 9600-row bf16-A one-plane GEMMs read 259 us per step on 46 against 230
+// on 44 in the step's kernel trace (they share the chip with the weight-gradient stream) although 46 wins isolated
+// (10.6 vs 12.1 us); keeping 44 there moved the step by nothing (7.069 / 7.100 / 7.107 ms vs 7.102 / 7.080 / 7.130).
+static int pick_glds_rounds(const mtts_conv_gemm_args &p, int M) {
+    static const int kPickable[] = {14, 15, 9, 10, 12, 13};  // 46 47 (160-row tiles) | 41 42 44 45
+    if (!(p.flags & (MTTS_GEMM_F_A_BF16 | MTTS_GEMM_F_W_SPLIT)) && glds_tiles(p, M) > 256) return MTTS_GEMM_GLDS + 13;
+    int best = -1;
+    double best_us = 0.;
+    for (int id : kPickable) {
+        if (!mtts::conv_gemm_glds_info(id, p).own) continue;
+        const GldsRounds r = glds_rounds(p, M, id, 1);
+        if (r.resident < 1) continue;
+        if (best < 0 || r.us < best_us) best = id, best_us = r.us;
+    }
+    return MTTS_GEMM_GLDS + best;
+}
 
 static int pick_cfg(const mtts_conv_gemm_args &p, int M, bool bf16) {
     // fp32: 64 x 64 tiles (config 3) on the text encoder's 3840-row GEMMs -- the best register schedule on every
@@ -1023,52 +1075,42 @@ static int pick_cfg(const mtts_conv_gemm_args &p, int M, bool bf16) {
     static const int d2 = [] { const char *e = getenv("MTTS_GEMM_F32_DEPTH2"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
     if (!bf16) return M <= 8192 ? (d2 == 1 ? 18 : 3) : (d2 == 0 ? 7 : 11);
     if (p.act == MTTS_ACT_GELU || p.act == MTTS_ACT_DGELU) return 7;
-    static const int sched_mask = [] {  // MTTS_GEMM_SCHED_OFF bit mask: A/B switch for experiments
-        const char *e = getenv("MTTS_GEMM_SCHED_OFF");
-        return e ? atoi(e) : 0;
-    }();
-    // 128 x 256 LDS-DMA tiles won the isolated sweep on the 19200-row N = 256 GEMMs (26.9 vs 29.8 us) but
-    // LOST 0.33 ms per step in an in-step A/B on one box (tools/gpu_ab.sh: 2829 vs 2915 utt/s): opt-in
-    if ((sched_mask & 4) && mtts::conv_gemm_glds_applies(p) && p.K >= 512) {  // 128 x 256 tiles, one round
-        const int t = ((M + 127) / 128) * ((p.N + 255) / 256);
-        if (t >= 128 && t <= 256) return MTTS_GEMM_GLDS + 14;
-    }
-    if (!(sched_mask & 2) && mtts::conv_gemm_glds_applies(p) && p.K >= 768) {
+    if (mtts::conv_gemm_glds_applies(p) && p.K >= 768) {
         const int t = glds_tiles(p, M);
-        if ((t >= 128 && t <= 256) || (t < 128 && p.K >= 1536 && p.N % 4 == 0)) return MTTS_GEMM_GLDS + 10;
-        // scalar-addressed LDS-DMA loop (whole-tap K steps): 64 x 64 two-stage tiles beat the register
-        // schedules on the 19200-row convs (tools/gemm_tall_sweep.py, profiles/r02/gemm_lean: 29.0 vs 29.7,
-        // 44.9 vs 48.5, 34.6 vs 38.3 us)
-        if (!(sched_mask & 8) && t > 256 && mtts::conv_gemm_glds_lean(p)) return MTTS_GEMM_GLDS + 13;
+        // the split-K rule's schedule: long reductions on grids far below the CU count (pick_splits)
+        if (t < 128 && p.K >= 1536 && p.N % 4 == 0) return MTTS_GEMM_GLDS + 10;
+        // scalar-addressed LDS-DMA loop (whole-tap K steps) from half a round of 64-row tiles up: the LDS-DMA
+        // kernels beat the register schedules there (profiles/r02/gemm_lean: 29.0 vs 29.7, 44.9 vs 48.5, 34.6 vs
+        // 38.3 us on the 19200-row convs; 17.4 vs 19.0 on the half-resolution ones); which one, by rounds
+        if (t >= 128 && mtts::conv_gemm_glds_lean(p)) return pick_glds_rounds(p, M);
+        if (t >= 128 && t <= 256) return MTTS_GEMM_GLDS + 10;
     }
-    if (!(sched_mask & 8) && p.K < 768 && p.N >= 512 && glds_tiles(p, M) >= 256 && mtts::conv_gemm_glds_applies(p) &&
+    if (p.K < 768 && p.N >= 512 && glds_tiles(p, M) >= 256 && mtts::conv_gemm_glds_applies(p) &&
         mtts::conv_gemm_glds_lean(p))
         return MTTS_GEMM_GLDS + 9;  // the decoder's q|k|v projection: 35.1 vs 37.2 us (one workgroup per CU:
                                     // not below one round of tiles -- the text encoder's 3840-row GEMMs)
     return p.K >= 384 ? 12 : 7;
 }
 
-// bf16 A (LDS-DMA only): 64 x 256 two-stage tiles when they fill the chip, 64 x 64 three-stage below
-// (profiles/r02/gemm_lean: 19.0 vs 21.0 us on the 19200 x 256 x 768 conv, 23.4 vs 32.7 on the q|k|v
-// projection; 13.2 vs 13.4 on the 9600-row conv, 16.5 vs 25.5 on the encoder's 3840 x 192 x 2304)
+// bf16 A (LDS-DMA only): by rounds for whole-tap K steps; other K layouts 64 x 256 two-stage tiles when they
+// fill the chip, 64 x 64 three-stage below (profiles/r02/gemm_lean: 19.0 vs 21.0 us on the 19200 x 256 x 768 conv,
+// 13.2 vs 13.4 on the 9600-row conv)
 static int pick_cfg_a16(const mtts_conv_gemm_args &p, int M) {
     if (p.act == MTTS_ACT_GELU || p.act == MTTS_ACT_DGELU) return MTTS_GEMM_GLDS + 12;
+    if (mtts::conv_gemm_glds_lean(p)) return pick_glds_rounds(p, M);
     return glds_tiles(p, M) >= 256 ? MTTS_GEMM_GLDS + 9 : MTTS_GEMM_GLDS + 12;
 }
 
 // Split weight planes (MTTS_GEMM_F_W_SPLIT, the parity policy's decoder forward): W's bytes double, which moves
 // the best schedules (step sweep with the split planes, tools/r3/gemm_step_sweep.py SWEEP_PREC=bf16-parity ->
 // profiles/r04/sweeps/ws_sweep.jsonl: 2655 -> ~2410 us per step): GELU epilogues keep the 32 x 128 register
-// tiles; whole-tap K steps take the LDS-DMA kernels -- 64 x 64 three-stage (bf16 A) / two-stage (fp32 A) on
-// the 19200-row N <= 256 GEMMs (31.6 vs 36.0 us, 36.5 vs 56.3), 64 x 256 elsewhere (9600 x 256 x 512: 17.0 vs
-// 30.6 on the register schedule the one-plane rule picks below K = 768); other K layouts the 32-wide register
-// tiles (19200 x 256 x 480: 32.8 vs 50.6 with 64-wide steps).
+// tiles; whole-tap K steps take the LDS-DMA kernels, the schedule by rounds (9600 x 256 x 512: 17.0 us on 64 x 256
+// tiles vs 30.6 on the register schedule the one-plane rule picks below K = 768); other K layouts the 32-wide
+// register tiles (19200 x 256 x 480: 32.8 vs 50.6 with 64-wide steps).
 static int pick_cfg_ws(const mtts_conv_gemm_args &p, int M) {
     if (p.act == MTTS_ACT_GELU || p.act == MTTS_ACT_DGELU) return 7;
     if (!mtts::conv_gemm_glds_applies(p) || !mtts::conv_gemm_glds_lean(p)) return 7;
-    const bool big = M >= 16384 && p.N <= 256;
-    if (p.flags & MTTS_GEMM_F_A_BF16) return big ? MTTS_GEMM_GLDS + 12 : MTTS_GEMM_GLDS + 9;
-    return M >= 16384 ? MTTS_GEMM_GLDS + 13 : MTTS_GEMM_GLDS + 9;
+    return pick_glds_rounds(p, M);
 }
 
 // Split-K (LDS-DMA schedules, heuristic pick only): grids below half the chip with >= 24 K steps
@@ -1267,6 +1309,31 @@ extern "C" size_t mtts_conv_gemm_workspace_size(const mtts_conv_gemm_args *args,
     int rc = MTTS_OK;
     const int cfg = resolve_cfg(*args, bf16, tile_cfg, args->nb * args->To, &rc);
     return rc ? 0 : plan_gemm(*args, bf16, cfg, splits).ws;
+}
+
+// Read-only plan of a call (host arithmetic only): the schedule and split count the launch would run -- through
+// resolve_cfg / plan_gemm, as the launch and the workspace-size query -- and, for an LDS-DMA schedule, how its
+// workgroups cover the chip (glds_rounds; zeros for the register and weight-stationary schedules).
+extern "C" int mtts_conv_gemm_plan(const mtts_conv_gemm_args *args, int32_t precision, int32_t tile_cfg,
+                                   int32_t splits, int32_t out[6]) {
+    MTTS_CHECK_ARG(args && out, "conv_gemm_plan: null argument");
+    MTTS_CHECK_ARG(precision == MTTS_PREC_BF16 || precision == MTTS_PREC_FP32, "conv_gemm_plan: bad precision");
+    MTTS_CHECK_ARG(splits >= 0, "conv_gemm_plan: bad split count");
+    const bool bf16 = precision == MTTS_PREC_BF16;
+    const int M = args->nb * args->To;
+    int rc = MTTS_OK;
+    const int cfg = resolve_cfg(*args, bf16, tile_cfg, M, &rc);
+    if (rc) return rc;
+    const GemmPlan pl = plan_gemm(*args, bf16, cfg, splits);
+    GldsRounds r = {};
+    int s = pl.splits;
+    if (pl.cfg >= MTTS_GEMM_GLDS && pl.cfg < MTTS_GEMM_WREG) {
+        if (pl.ws == 0) s = 1;
+        r = glds_rounds(*args, M, pl.cfg - MTTS_GEMM_GLDS, s);
+        if (s > 1) s = (int)(pl.ws / ((size_t)M * args->N * sizeof(float)));  // every split non-empty
+    }
+    out[0] = pl.cfg, out[1] = s, out[2] = r.tiles, out[3] = r.resident, out[4] = r.rounds, out[5] = r.fill_pm;
+    return MTTS_OK;
 }
 
 extern "C" int mtts_conv_gemm_ws(const mtts_conv_gemm_args *args, int32_t precision, int32_t tile_cfg, int32_t splits,

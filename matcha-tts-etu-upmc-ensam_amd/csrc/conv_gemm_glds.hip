@@ -74,13 +74,24 @@ constexpr uint32_t MTTS_GLDS_OOB = mtts::kDmaOob;
 
 template <int WM, int WN, int TM, int TN, int STAGES, bool ABF16 = false, int NPL = 1>
 struct GldsGeom {
-    static constexpr int NT = 64 * WM * WN;
+    static constexpr int NT = 64 * WM * WN, NW = WM * WN;
     static constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
     static constexpr int A_BYTES = BM * kBK * (ABF16 ? 2 : 4);  // fp32 rows of 256 B / bf16 rows of 128 B
     static constexpr int W_BYTES = NPL * BN * kBK * 2;  // bf16 rows of 128 B (NPL weight planes: BN rows each)
-    static constexpr int GA = A_BYTES / (NT * 16);  // DMA instructions per thread per K step
-    static constexpr int GW = W_BYTES / (NT * 16);
-    static_assert(A_BYTES % (NT * 16) == 0 && W_BYTES % (NT * 16) == 0, "tile / threads mismatch");
+    // An image is NIA / NIW wave instructions of 1 KiB.  Wave w issues instructions w, w + NW, ...: GA / GW
+    // per K step, the last one only by the waves below RA / RW when the image does not divide over the waves
+    // (160-row tiles: five or ten waves on a 16 KiB W image) -- a ragged split, RA / RW != 0
+    static constexpr int NIA = A_BYTES / 1024, NIW = W_BYTES / 1024;
+    static constexpr int GA = (NIA + NW - 1) / NW, GW = (NIW + NW - 1) / NW;
+    static constexpr int RA = NIA % NW, RW = NIW % NW;
+    static constexpr bool RAGGED = RA != 0 || RW != 0;
+    static_assert(A_BYTES % 1024 == 0 && W_BYTES % 1024 == 0, "whole DMA instructions");
+    static_assert(STAGES >= 2 && STAGES <= 4, "two to four stage buffers");
+    // Epilogue staging: one 4 KiB image per wave, carved from the first two stages' buffers.  Up to 8 waves keep
+    // the (wave % 4 -> buffer, wave / 4 -> slot) layout; more waves take consecutive slots of sA0, sW0, sA1, sW1
+    static constexpr int SA = A_BYTES / 4096, SW = W_BYTES / 4096;
+    static_assert(NW <= 8 ? (SA >= (NW + 3) / 4 && SW >= (NW + 2) / 4) : 2 * (SA + SW) >= NW,
+                  "the epilogue's per-wave staging images fit the stage buffers");
 };
 
 // ABF16: A is bf16 in HBM (MTTS_GEMM_F_A_BF16): 128-byte rows, the same image and swizzle as W, and
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
     constexpr int RPI = ABF16 ? 8 : 4;       // A rows per 1 KiB DMA instruction
     constexpr int CPR = ABF16 ? 8 : 16;      // 16-byte chunks per A row of one K step
     constexpr int EPC = 16 / ES;             // A elements per chunk
-    constexpr int NT = G::NT, BM = G::BM, BN = G::BN, GA = G::GA, GW = G::GW, NW = NT / 64;
+    constexpr int NT = G::NT, BM = G::BM, BN = G::BN, GA = G::GA, GW = G::GW, NW = G::NW;
     // one __shared__ object per stage and operand, and a K loop unrolled by STAGES so every access
     // names its buffer statically: hipcc then sees that a DMA into one buffer cannot alias the
     // ds_reads of another and does not insert vmcnt(0) before them (one shared array with a runtime
@@ -114,15 +125,19 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
     __shared__ __attribute__((aligned(1024))) unsigned char sA1[G::A_BYTES], sW1[G::W_BYTES];
     __shared__ __attribute__((aligned(1024))) unsigned char sA2[STAGES > 2 ? G::A_BYTES : 16],
         sW2[STAGES > 2 ? G::W_BYTES : 16];
+    __shared__ __attribute__((aligned(1024))) unsigned char sA3[STAGES > 3 ? G::A_BYTES : 16],
+        sW3[STAGES > 3 ? G::W_BYTES : 16];
     auto abuf = [&](auto S) -> unsigned char * {
         if constexpr (decltype(S)::value == 0) return sA0;
         else if constexpr (decltype(S)::value == 1) return sA1;
-        else return sA2;
+        else if constexpr (decltype(S)::value == 2) return sA2;
+        else return sA3;
     };
     auto wbuf = [&](auto S) -> unsigned char * {
         if constexpr (decltype(S)::value == 0) return sW0;
         else if constexpr (decltype(S)::value == 1) return sW1;
-        else return sW2;
+        else if constexpr (decltype(S)::value == 2) return sW2;
+        else return sW3;
     };
     // LDS byte addresses of the stage buffers, cast from the __shared__ objects themselves (a constant:
     // no generic-pointer null check)
@@ -131,12 +146,14 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
     auto abuf_l = [&](auto S) -> uint32_t {
         if constexpr (decltype(S)::value == 0) return lds_addr((const lds_u8 *)sA0);
         else if constexpr (decltype(S)::value == 1) return lds_addr((const lds_u8 *)sA1);
-        else return lds_addr((const lds_u8 *)sA2);
+        else if constexpr (decltype(S)::value == 2) return lds_addr((const lds_u8 *)sA2);
+        else return lds_addr((const lds_u8 *)sA3);
     };
     auto wbuf_l = [&](auto S) -> uint32_t {
         if constexpr (decltype(S)::value == 0) return lds_addr((const lds_u8 *)sW0);
         else if constexpr (decltype(S)::value == 1) return lds_addr((const lds_u8 *)sW1);
-        else return lds_addr((const lds_u8 *)sW2);
+        else if constexpr (decltype(S)::value == 2) return lds_addr((const lds_u8 *)sW2);
+        else return lds_addr((const lds_u8 *)sW3);
     };
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -144,6 +161,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
     const int wr = wave / WN, wc = wave % WN;
     const int lr = lane & 31, lh = lane >> 5;
     const int M = p.nb * p.To;
+    // ragged split: whether this wave issues the last A / W instruction of a K step (wave-uniform)
+    const bool a_last = G::RA == 0 || wave < G::RA, w_last = G::RW == 0 || wave < G::RW;
     // split-K (part != NULL): grid = tiles x S, the S splits of a tile adjacent (same XCD); split s
     // reduces K steps [s*ksteps, min(nk, (s+1)*ksteps)) and stores raw fp32 partials to part[s][M][N]
     int m0, n0, kstep0 = 0, nk = (p.K + kBK - 1) / kBK;
@@ -254,10 +273,12 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
             const uint32_t la = abuf_l(S), lw = wbuf_l(S);
 #pragma unroll
             for (int i = 0; i < GA; ++i)
-                bload16(l_vo[i], l_rsa, l_soa, __builtin_amdgcn_readfirstlane(la + (i * NW + wave) * 1024));
+                if (i < GA - 1 || a_last)
+                    bload16(l_vo[i], l_rsa, l_soa, __builtin_amdgcn_readfirstlane(la + (i * NW + wave) * 1024));
 #pragma unroll
             for (int i = 0; i < GW; ++i)
-                bload16(l_vw[i], l_rsw, l_sow, __builtin_amdgcn_readfirstlane(lw + (i * NW + wave) * 1024));
+                if (i < GW - 1 || w_last)
+                    bload16(l_vw[i], l_rsw, l_sow, __builtin_amdgcn_readfirstlane(lw + (i * NW + wave) * 1024));
             l_sow += kBK * 2;
             l_soa += kBK * ES;
             if (--l_chs == 0) {  // next tap (wave-uniform branch; nothing in flight depends on registers)
@@ -274,8 +295,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
 #pragma unroll
         for (int i = 0; i < GA; ++i) {
             const bool ok = (a_ok[i] >> min(a_j[i], 31)) & 1u;  // a_j >= ntaps (past K): bit is 0
-            glds16(ok ? static_cast<const void *>(a_src[i]) : static_cast<const void *>(zero),
-                   abase + (i * NW + wave) * 1024);
+            if (i < GA - 1 || a_last)
+                glds16(ok ? static_cast<const void *>(a_src[i]) : static_cast<const void *>(zero),
+                       abase + (i * NW + wave) * 1024);
             a_ch[i] += kBK;
             a_src[i] += kBK * ES;
             const bool w = a_ch[i] >= p.cin;  // cin >= 64: at most one tap change per step
@@ -286,8 +308,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
 #pragma unroll
         for (int i = 0; i < GW; ++i) {
             const bool ok = w_nok[i] && w_k[i] < p.Kp;
-            glds16(ok ? static_cast<const void *>(w_ptr[i]) : static_cast<const void *>(zero),
-                   wbase + (i * NW + wave) * 1024);
+            if (i < GW - 1 || w_last)
+                glds16(ok ? static_cast<const void *>(w_ptr[i]) : static_cast<const void *>(zero),
+                       wbase + (i * NW + wave) * 1024);
             w_ptr[i] += kBK;
             w_k[i] += kBK;
         }
@@ -408,13 +431,24 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
     // prologue: steps 0 .. STAGES-2 in flight (steps past nk DMA zeros into their buffer: harmless)
     issue(std::integral_constant<int, 0>{});
     if constexpr (STAGES > 2) issue(std::integral_constant<int, 1>{});
+    if constexpr (STAGES > 3) issue(std::integral_constant<int, 2>{});
     MTTS_TLG(2);
     // step kt uses buffer kt % STAGES and refills buffer (kt + STAGES - 1) % STAGES, which step kt-1 read
     int tl_k = 0;
     (void)tl_k;
     auto step = [&](auto S) {
         constexpr int cur = decltype(S)::value, nxt = (cur + STAGES - 1) % STAGES;
-        wait_vmcnt<(GA + GW) * (STAGES - 2)>();  // this wave's DMAs for step kt have landed
+        // this wave's DMAs for step kt have landed: all but the STAGES - 2 later steps' -- a count of the wave's
+        // own instructions per step, so with a ragged split each wave waits on its own constant
+        constexpr int F = (GA + GW) * (STAGES - 2);
+        if constexpr (!G::RAGGED || STAGES == 2) {
+            wait_vmcnt<F>();
+        } else {
+            const int less = (a_last ? 0 : 1) + (w_last ? 0 : 1);  // wave-uniform
+            if (less == 0) wait_vmcnt<F>();
+            else if (less == 1) wait_vmcnt<F - (STAGES - 2)>();
+            else wait_vmcnt<F - 2 * (STAGES - 2)>();
+        }
         mtts::lds_barrier();                       // ... everyone's, and step kt-1's reads are done
 #if MTTS_GEMM_TIMELINE
         if (tl_k < kTlSteps) MTTS_TLG(3 + 2 * tl_k);
@@ -435,13 +469,26 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(mtts_conv_
             if (kt + 2 >= nk) break;
             step(std::integral_constant<int, 2>{});
         }
+        if constexpr (STAGES > 3) {
+            if (kt + 3 >= nk) break;
+            step(std::integral_constant<int, 3>{});
+        }
     }
     wait_vmcnt<0>();  // no DMA may still target this workgroup's LDS when it retires
     MTTS_TLG(kTlSlots - 2);
     if (part || mtts::gemm_epilogue_vec_ok(p)) {
         mtts::lds_barrier();  // every wave is past its last fragment read: the buffers are free
-        unsigned char *stage = wave % 4 == 0 ? sA0 : wave % 4 == 1 ? sW0 : wave % 4 == 2 ? sA1 : sW1;
-        float *st = reinterpret_cast<float *>(stage + (wave / 4) * 4096);
+        unsigned char *stage;
+        if constexpr (NW <= 8) {
+            stage = (wave % 4 == 0 ? sA0 : wave % 4 == 1 ? sW0 : wave % 4 == 2 ? sA1 : sW1) + (wave / 4) * 4096;
+        } else {  // consecutive 4 KiB slots of sA0, sW0, sA1, sW1 (GldsGeom asserts that they hold NW images)
+            constexpr int SA = G::SA, SW = G::SW;
+            stage = wave < SA ? sA0 + wave * 4096
+                    : wave < SA + SW ? sW0 + (wave - SA) * 4096
+                    : wave < 2 * SA + SW ? sA1 + (wave - SA - SW) * 4096
+                                         : sW1 + (wave - 2 * SA - SW) * 4096;
+        }
+        float *st = reinterpret_cast<float *>(stage);
         if (part)
             mtts::gemm_store_partial<TM, TN>(p, acc, st, part + (size_t)(kstep0 / ksteps) * M * p.N,
                                              m0 + wr * 32 * TM, n0 + wc * 32 * TN, lane);
@@ -481,29 +528,91 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(mtts_conv_gemm_arg
     mtts::epilogue_row4(p, b * p.To_full + u * p.out_stride + p.out_off, n, e, s0, s1, keep);
 }
 
+// Operand kinds: A storage x weight planes.  A schedule has an instantiation per kind in its mask.
+enum : unsigned { kF32 = 1u, kB16 = 2u, kF32WS = 4u, kB16WS = 8u, kX3 = 16u };
+constexpr int kNumKinds = 5;
+constexpr bool kind_a16(int kind) { return kind == 1 || kind == 3; }
+constexpr int kind_planes(int kind) { return kind == 4 ? 3 : kind >= 2 ? 2 : 1; }
+inline int kind_of(const mtts_conv_gemm_args &p) {
+    if (p.flags & MTTS_GEMM_F_SPLIT3) return 4;
+    return ((p.flags & MTTS_GEMM_F_W_SPLIT) ? 2 : 0) + ((p.flags & MTTS_GEMM_F_A_BF16) ? 1 : 0);
+}
+
 struct GldsCfg {
     int wm, wn, tm, tn, stages;
-    bool f32a, bf16a;  // which A storages have an instantiation (LDS <= 160 KiB, registers)
+    unsigned kinds;  // operand kinds with an instantiation (LDS <= 160 KiB, registers)
+    bool lean_only = false;  // only the scalar-addressed loop is built (the register-addressed one spills)
 };
+// Stage bytes = A image + W image of one K step (64 x BM x 2 or 4 bytes, planes x 64 x BN x 2 bytes); LDS per
+// workgroup = stages x stage bytes; resident workgroups per CU = min(160 KiB / LDS, 2048 threads / workgroup)
+// (glds_resident, which also names the one instantiation whose registers bind; the 160-row figures are below).  Two figures size a
+// schedule: resident x LDS <= 160 KiB, and the bytes in flight per CU during the K loop,
+// (stages - 1) x stage bytes x resident, near or above the ~96 KB that cover the 1.1 us DMA latency at the
+// 75-95 GB/s per-CU fill ceiling.  The 160-row tiles (46, 47; 160 = 5 x 32 divides the decoder's 9600 and 19200
+// rows: 60 / 120 row tiles instead of 150 / 300, so 240 or 480 workgroups on the chip's 256 or 512 slots) per
+// kind, stage bytes -> LDS, resident, in flight:
+//   46 160 x 64  2 st  bf16 A 2 pl  20+16 = 36 KiB ->  72 KiB, 2 resident (144 KiB),  72 KiB in flight
+//                      bf16 A 1 pl  20+ 8 = 28 KiB ->  56 KiB, 2 resident (112 KiB),  56 KiB
+//                      fp32 A 2 pl  40+16 = 56 KiB -> 112 KiB, 1 resident,            56 KiB (thin)
+//                      fp32 A 1 pl  40+ 8 = 48 KiB ->  96 KiB, 1 resident,            48 KiB (thin)
+//   47 160 x 128 3 st  bf16 A 2 pl  20+32 = 52 KiB -> 156 KiB, 1 resident, 104 KiB; 1 pl 36 KiB -> 108 KiB, 1, 72 KiB
+// Registers (kernel-resource-usage; no AGPRs, scratch 0): 46 with bf16 A, two resident = 5 waves per SIMD, so <= 96:
+// 80 / 77 VGPRs (2 / 1 planes; register-addressed loop 93 / 86); 46 with fp32 A, one resident = 3 waves per SIMD, so
+// <= 168: 94 / 94 (123 / 114); 47, one resident: 165 / 150 -- its register-addressed loop needs 168 + 148 bytes of
+// scratch with two planes, so 47 is built for whole-tap K steps only and runs 41 otherwise.
+// Measured and not kept: 160 x 64 with four stages (one resident, 108 KiB in flight: 2-5 % behind the
+// two-stage 46 on every 9600-row shape, 3-27 % on the 19200-row ones) and 160 x 32 with three stages for fp32 A
+// (five waves, 1.7-2x slower than 46: ten DMA instructions per wave and step).
 constexpr GldsCfg kGlds[] = {
-    {1, 4, 2, 2, 2, true, false},   // 32: 64 x 256, 256 thr, 2 stages (96 KiB)
-    {1, 4, 2, 2, 3, false, false},  // 33: 64 x 256, 3 stages (144 KiB; fp32 A spills: 7x slower)
-    {2, 2, 2, 2, 2, true, false},   // 34: 128 x 128, 2 stages (96 KiB)
-    {2, 2, 2, 2, 3, false, false},  // 35: 128 x 128, 3 stages (144 KiB; fp32 A spills: 7x slower)
-    {1, 4, 1, 2, 2, true, false},   // 36: 32 x 256, 2 stages (80 KiB)
-    {1, 4, 1, 2, 3, true, false},   // 37: 32 x 256, 3 stages (120 KiB)
-    {2, 2, 1, 2, 2, true, false},   // 38: 64 x 128, 2 stages (64 KiB)
-    {2, 2, 1, 2, 3, true, false},   // 39: 64 x 128, 3 stages (96 KiB)
-    {1, 4, 1, 1, 3, true, false},   // 40: 32 x 128, 3 stages (72 KiB)
-    {2, 4, 1, 2, 2, true, true},    // 41: 64 x 256, 512 thr (waves 32 x 64), 2 stages (96 KiB)
-    {2, 4, 1, 2, 3, true, true},    // 42: 64 x 256, 512 thr, 3 stages (144 KiB)
-    {1, 2, 2, 2, 3, true, false},   // 43: 64 x 128, 128 thr (waves 64 x 64), 3 stages (96 KiB)
-    {2, 2, 1, 1, 3, true, true},    // 44: 64 x 64, 3 stages (72 KiB)
-    {2, 2, 1, 1, 2, true, false},   // 45: 64 x 64, 2 stages (48 KiB)
-    {2, 4, 2, 2, 2, true, true},    // 46: 128 x 256, 512 thr (waves 64 x 64), 2 stages (128 KiB)
-    {4, 2, 1, 2, 2, true, false},   // 47: 128 x 128, 512 thr (waves 32 x 64), 2 stages (96 KiB)
+    {1, 4, 2, 2, 2, kF32},   // 32: 64 x 256, 256 thr, 2 stages (96 KiB)
+    {1, 4, 2, 2, 3, 0},      // 33: 64 x 256, 3 stages (144 KiB; fp32 A spills: 7x slower)
+    {2, 2, 2, 2, 2, kF32},   // 34: 128 x 128, 2 stages (96 KiB)
+    {2, 2, 2, 2, 3, 0},      // 35: 128 x 128, 3 stages (144 KiB; fp32 A spills: 7x slower)
+    {1, 4, 1, 2, 2, kF32},   // 36: 32 x 256, 2 stages (80 KiB)
+    {1, 4, 1, 2, 3, kF32},   // 37: 32 x 256, 3 stages (120 KiB)
+    {2, 2, 1, 2, 2, kF32},   // 38: 64 x 128, 2 stages (64 KiB)
+    {2, 2, 1, 2, 3, kF32},   // 39: 64 x 128, 3 stages (96 KiB)
+    {1, 4, 1, 1, 3, kF32},   // 40: 32 x 128, 3 stages (72 KiB)
+    {2, 4, 1, 2, 2, kF32 | kB16 | kF32WS | kB16WS},  // 41: 64 x 256, 512 thr (waves 32 x 64), 2 stages (96 KiB; split
+                                                      // W: 144 KiB with bf16 A, 160 KiB with fp32 A)
+    {2, 4, 1, 2, 3, kF32 | kB16},                     // 42: 64 x 256, 512 thr, 3 stages (144 KiB)
+    {1, 2, 2, 2, 3, kF32},                            // 43: 64 x 128, 128 thr (waves 64 x 64), 3 stages (96 KiB)
+    {2, 2, 1, 1, 3, kF32 | kB16 | kF32WS | kB16WS | kX3},  // 44: 64 x 64, 3 stages (72 KiB; bf16x6: 120 KiB)
+    {2, 2, 1, 1, 2, kF32 | kF32WS | kX3},             // 45: 64 x 64, 2 stages (48 KiB)
+    {5, 2, 1, 1, 2, kF32 | kB16 | kF32WS | kB16WS},   // 46: 160 x 64, 640 thr (waves 32 x 32), 2 stages
+    {5, 2, 1, 2, 3, kB16 | kB16WS, true},             // 47: 160 x 128, 640 thr (waves 32 x 64), 3 stages
 };
 constexpr int kNumGlds = sizeof(kGlds) / sizeof(kGlds[0]);
+
+// The instantiation schedule c runs for an operand kind: its own where it has one; else, as before the table,
+//  * three planes (bf16x6): 64 x 64 three-stage (44) or two-stage (45) by the schedule's stage count;
+//  * split weights: 64 x 256 two-stage (41) for tiles >= 128 wide, else 64 x 64 three- (44) / two-stage (45; bf16 A:
+//    41) by the stage count (a 128 x 128 two-stage split-weight instance, round 4, ran 3-5x slower than the 64-row
+//    ones on the FFN up-projection -- profiles/r04/sweeps/ff1_probe.txt -- and was removed);
+//  * one plane: 64 x 256 two-stage (41).
+constexpr int glds_run_id(int c, int kind, bool lean = true) {
+    if (kGlds[c].lean_only && !lean) return 9;
+    if (kGlds[c].kinds & (1u << kind)) return c;
+    if (kind == 4) return kGlds[c].stages >= 3 ? 12 : 13;
+    if (kind >= 2) {
+        const int w = kGlds[c].wn * kGlds[c].tn * 32 >= 128 ? 9 : (kGlds[c].stages == 2 ? 13 : 12);
+        return (kGlds[w].kinds & (1u << kind)) ? w : 9;
+    }
+    return 9;
+}
+constexpr int glds_bm(int c) { return 32 * kGlds[c].wm * kGlds[c].tm; }
+constexpr int glds_bn(int c) { return 32 * kGlds[c].wn * kGlds[c].tn; }
+constexpr int glds_stage_bytes(int c, int kind) {
+    return glds_bm(c) * kBK * (kind_a16(kind) ? 2 : 4) + kind_planes(kind) * glds_bn(c) * kBK * 2;
+}
+constexpr int glds_resident(int c, int kind, bool lean = true) {
+    // the one instantiation whose registers bind: 41 with a bf16 A and one plane, register-addressed loop -- 140 VGPRs,
+    // three waves per SIMD, one 8-wave workgroup (80 KiB of LDS would admit two; its scalar-addressed loop: 108, two)
+    if (c == 9 && kind == 1 && !lean) return 1;
+    const int lds = kGlds[c].stages * glds_stage_bytes(c, kind), nt = 64 * kGlds[c].wm * kGlds[c].wn;
+    const int by_lds = 160 * 1024 / lds, by_thr = 2048 / nt;
+    return by_lds < by_thr ? by_lds : by_thr;
+}
 
 }  // namespace
 
@@ -522,18 +631,29 @@ bool conv_gemm_glds_lean(const mtts_conv_gemm_args &p) {
 
 namespace {
 
-template <int C, bool ABF16, bool WS = false, bool X3 = false>
-int launch_glds_t(const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
+template <int C, int KIND>
+auto glds_kernel(bool lean) {
     constexpr GldsCfg c = kGlds[C];
-    using G = GldsGeom<c.wm, c.wn, c.tm, c.tn, c.stages, ABF16, X3 ? 3 : (WS ? 2 : 1)>;
-    static_assert((!WS && !X3) || c.stages * (G::A_BYTES + G::W_BYTES) <= 160 * 1024, "split-weight stages fit LDS");
-    auto kern = mtts::conv_gemm_glds_lean(p) ? conv_gemm_glds_kernel<c.wm, c.wn, c.tm, c.tn, c.stages, ABF16, true, WS, X3>
-                                : conv_gemm_glds_kernel<c.wm, c.wn, c.tm, c.tn, c.stages, ABF16, false, WS, X3>;
+    constexpr bool A16 = kind_a16(KIND), WS = KIND == 2 || KIND == 3, X3 = KIND == 4;
+    if constexpr (c.lean_only) {
+        return conv_gemm_glds_kernel<c.wm, c.wn, c.tm, c.tn, c.stages, A16, true, WS, X3>;
+    } else {
+        return lean ? conv_gemm_glds_kernel<c.wm, c.wn, c.tm, c.tn, c.stages, A16, true, WS, X3>
+                    : conv_gemm_glds_kernel<c.wm, c.wn, c.tm, c.tn, c.stages, A16, false, WS, X3>;
+    }
+}
+
+template <int C, int KIND>
+int launch_glds_t(const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
+    static_assert(kGlds[C].kinds & (1u << KIND), "an instantiated kind");
+    static_assert(glds_resident(C, KIND) >= 1, "the stages fit LDS");
+    constexpr int BM = glds_bm(C), BN = glds_bn(C), NT = 64 * kGlds[C].wm * kGlds[C].wn;
+    auto kern = glds_kernel<C, KIND>(mtts::conv_gemm_glds_lean(p));
     const int nk = (p.K + kBK - 1) / kBK;
     const int ksteps = (nk + splits - 1) / splits;
     const int S = splits > 1 ? (nk + ksteps - 1) / ksteps : 1;  // every split non-empty
-    dim3 grid((unsigned)(((M + G::BM - 1) / G::BM) * ((p.N + G::BN - 1) / G::BN) * S));
-    hipLaunchKernelGGL(kern, grid, dim3(G::NT), 0, st, p, ksteps, S > 1 ? part : nullptr);
+    dim3 grid((unsigned)(((M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * S));
+    hipLaunchKernelGGL(kern, grid, dim3(NT), 0, st, p, ksteps, S > 1 ? part : nullptr);
     int rc = mtts::check_launch("conv_gemm_glds");
     if (rc || S == 1) return rc;
     const long long n4 = (long long)M * (p.N / 4);
@@ -542,38 +662,48 @@ int launch_glds_t(const mtts_conv_gemm_args &p, int M, int splits, float *part, 
     return mtts::check_launch("splitk_epilogue_kernel");
 }
 
-// Split-weight operands (MTTS_GEMM_F_W_SPLIT) run three instantiations: 64 x 64 three-stage (44) or
-// two-stage (45), and 64 x 256 two-stage (41, 144 KiB with bf16 A, 160 KiB with fp32 A) for the wide tiles
-// (a 128 x 128 two-stage split-weight instance, round 4, ran 3-5x slower than the 64-row ones on the FFN
-// up-projection -- tools/r4/ff1_probe.py, profiles/r04/sweeps/ff1_probe.txt -- and was removed)
-template <int C>
-int launch_glds_ws(const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
-    constexpr int W = kGlds[C].wn * kGlds[C].tn * 32 >= 128 ? 9 : (kGlds[C].stages == 2 ? 13 : 12);
-    if (p.flags & MTTS_GEMM_F_A_BF16) {
-        if constexpr (kGlds[W].bf16a) return launch_glds_t<W, true, true>(p, M, splits, part, st);
-        else return launch_glds_t<9, true, true>(p, M, splits, part, st);
-    }
-    return launch_glds_t<W, false, true>(p, M, splits, part, st);
-}
-
-// bf16x6 (MTTS_GEMM_F_SPLIT3, fp32 A): 64 x 64 tiles, three stages (44: 120 KiB) or two (45)
-template <int C>
-int launch_glds_x3(const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
-    if constexpr (kGlds[C].stages >= 3) return launch_glds_t<12, false, false, true>(p, M, splits, part, st);
-    else return launch_glds_t<13, false, false, true>(p, M, splits, part, st);
-}
-
-// A schedule without an instantiation for the operand's storage runs the 64 x 256 two-stage one (41)
 template <int C>
 int launch_glds(const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
-    if (p.flags & MTTS_GEMM_F_SPLIT3) return launch_glds_x3<C>(p, M, splits, part, st);
-    if (p.flags & MTTS_GEMM_F_W_SPLIT) return launch_glds_ws<C>(p, M, splits, part, st);
-    if (p.flags & MTTS_GEMM_F_A_BF16) {
-        if constexpr (kGlds[C].bf16a) return launch_glds_t<C, true>(p, M, splits, part, st);
-        else return launch_glds_t<9, true>(p, M, splits, part, st);
+    if constexpr (kGlds[C].lean_only) {
+        if (!mtts::conv_gemm_glds_lean(p)) return launch_glds<9>(p, M, splits, part, st);
     }
-    if constexpr (kGlds[C].f32a) return launch_glds_t<C, false>(p, M, splits, part, st);
-    else return launch_glds_t<9, false>(p, M, splits, part, st);
+    switch (kind_of(p)) {
+        case 4: return launch_glds_t<glds_run_id(C, 4), 4>(p, M, splits, part, st);
+        case 3: return launch_glds_t<glds_run_id(C, 3), 3>(p, M, splits, part, st);
+        case 2: return launch_glds_t<glds_run_id(C, 2), 2>(p, M, splits, part, st);
+        case 1: return launch_glds_t<glds_run_id(C, 1), 1>(p, M, splits, part, st);
+        default: return launch_glds_t<glds_run_id(C, 0), 0>(p, M, splits, part, st);
+    }
+}
+
+// hipOccupancyMaxActiveBlocksPerMultiprocessor of schedule C's own instantiation for a kind (-1: none)
+template <int C>
+int occupancy_glds(int kind, bool lean) {
+    int n = -1;
+    auto ask = [&](auto K) {
+        constexpr int KIND = decltype(K)::value;
+        if constexpr ((kGlds[C].kinds & (1u << KIND)) != 0) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, glds_kernel<C, KIND>(lean), 64 * kGlds[C].wm * kGlds[C].wn,
+                                                             0) != hipSuccess)
+                n = -2;
+        }
+    };
+    switch (kind) {
+        case 0: ask(std::integral_constant<int, 0>{}); break;
+        case 1: ask(std::integral_constant<int, 1>{}); break;
+        case 2: ask(std::integral_constant<int, 2>{}); break;
+        case 3: ask(std::integral_constant<int, 3>{}); break;
+        case 4: ask(std::integral_constant<int, 4>{}); break;
+        default: break;
+    }
+    return n;
+}
+
+template <int... I>
+int occupancy_glds_id(int id, int kind, bool lean, std::integer_sequence<int, I...>) {
+    int n = -1;
+    ((id == I ? (n = occupancy_glds<I>(kind, lean), true) : false) || ...);
+    return n;
 }
 
 template <int... I>
@@ -618,7 +748,38 @@ int splitk_combine(const mtts_conv_gemm_args &p, int M, const float *part, int S
 int conv_gemm_glds_launch(int id, const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
     return launch_glds_id(id, p, M, splits, part, st, std::make_integer_sequence<int, kNumGlds>{});
 }
+
+// The tile, stage bytes and resident workgroups per CU of the instantiation that schedule `id` runs for p's
+// operand kind (glds_run_id: the launch's own mapping), from the table beside kGlds[].
+GldsInfo conv_gemm_glds_info(int id, const mtts_conv_gemm_args &p) {
+    const int kind = kind_of(p);
+    GldsInfo g = {};
+    if (id < 0 || id >= kNumGlds) return g;
+    const int r = glds_run_id(id, kind, conv_gemm_glds_lean(p));
+    g.run_id = r;
+    g.bm = glds_bm(r);
+    g.bn = glds_bn(r);
+    g.stages = kGlds[r].stages;
+    g.stage_bytes = glds_stage_bytes(r, kind);
+    g.resident = glds_resident(r, kind, conv_gemm_glds_lean(p));
+    g.own = r == id;
+    return g;
+}
 }  // namespace mtts
+
+// Table figure and the runtime's answer for one instantiation (tests): out[0] = the table's resident workgroups per
+// CU, out[1] = hipOccupancyMaxActiveBlocksPerMultiprocessor.  kind: 0 fp32 A, 1 bf16 A, 2 / 3 the same with split
+// weights, 4 three planes.  MTTS_ERR_INVALID_ARG when the schedule has no instantiation of its own for the kind.
+extern "C" int mtts_conv_gemm_glds_occupancy(int32_t schedule, int32_t kind, int32_t lean, int32_t out[2]) {
+    const int id = schedule - MTTS_GEMM_GLDS;
+    MTTS_CHECK_ARG(out && id >= 0 && id < kNumGlds && kind >= 0 && kind < kNumKinds &&
+                       (kGlds[id].kinds & (1u << kind)) && (lean || !kGlds[id].lean_only),
+                   "conv_gemm_glds_occupancy: no such instantiation");
+    out[0] = glds_resident(id, kind, lean != 0);
+    out[1] = occupancy_glds_id(id, kind, lean != 0, std::make_integer_sequence<int, kNumGlds>{});
+    if (out[1] < 0) return mtts::fail(MTTS_ERR_HIP, "conv_gemm_glds_occupancy: occupancy query failed");
+    return MTTS_OK;
+}
 
 #if MTTS_GEMM_TIMELINE
 // diagnostic builds: copy (or zero, host == NULL) the LDS-DMA kernels' timeline buffer; returns its size in bytes

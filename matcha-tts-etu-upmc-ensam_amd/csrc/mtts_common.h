@@ -53,6 +53,15 @@ bool conv_gemm_glds_lean(const mtts_conv_gemm_args &p);  // whole-tap K steps: s
 // splits > 1: split-K into `part` (conv_gemm_glds_splitk_bytes of workspace) + a combine/epilogue pass
 int conv_gemm_glds_launch(int id, const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st);
 size_t conv_gemm_glds_splitk_bytes(const mtts_conv_gemm_args &p, int splits);
+// what schedule id launches for p's operand kind (A storage x weight planes), from the table beside kGlds[]
+struct GldsInfo {
+    int run_id;       // the instantiation that runs (id itself when `own`)
+    int bm, bn, stages;
+    int stage_bytes;  // A image + W image of one K step
+    int resident;     // workgroups per CU, from LDS and threads
+    bool own;
+};
+GldsInfo conv_gemm_glds_info(int id, const mtts_conv_gemm_args &p);
 }  // namespace mtts
 
 struct mtts_reduce_job;
