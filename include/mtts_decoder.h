@@ -107,10 +107,14 @@ typedef struct mtts_conv_gemm_args {
                                         results at bf16 MFMA rates (the parity policy's text encoder forward) */
 
 int mtts_conv_gemm(const mtts_conv_gemm_args *args, int32_t precision, void *hip_stream);
-/* Same, with an explicit schedule: 0..17 = register-staged tile configs (csrc/conv_gemm.hip kCfgs;
- * 8..17 bf16-only: 64-wide K steps, two K steps in flight), MTTS_GEMM_GLDS + i = the bf16 LDS-DMA schedules
- * (csrc/conv_gemm_glds.hip), MTTS_GEMM_WREG = the weight-stationary schedule (csrc/conv_gemm_wreg.hip), -1 = heuristic.
- * For tuning and tests; mtts_conv_gemm picks the configuration itself. */
+/* Same, with an explicit schedule.  The ids keep the numbers of the tuning rounds' tables; the schedules built:
+ *   register-staged (csrc/conv_gemm.hip kCfgs): 7 (both precisions), 12 (bf16 only), 3, 11 and 18 (fp32 only);
+ *   bf16 LDS-DMA (csrc/conv_gemm_glds.hip kGlds): 41, 42, 44, 45, 46 and 47;
+ *   MTTS_GEMM_WREG: the bf16 weight-stationary schedule (csrc/conv_gemm_wreg.hip);
+ *   -1: the heuristic.
+ * Any other id, or a register-staged id in the precision it is not built for, is MTTS_ERR_INVALID_ARG ("bad tile
+ * config") from this call, mtts_conv_gemm_ws and mtts_conv_gemm_plan, and 0 bytes from
+ * mtts_conv_gemm_workspace_size, before any launch.  For tests; mtts_conv_gemm picks the schedule itself. */
 int mtts_conv_gemm_tile(const mtts_conv_gemm_args *args, int32_t precision, int32_t tile_cfg, void *hip_stream);
 /* With a caller-owned workspace: lets the bf16 LDS-DMA schedules split K over several workgroups
  * (fp32 partial slabs, combined in a fixed order by a second kernel that also runs the epilogue) when
@@ -129,7 +133,7 @@ int mtts_conv_gemm_ws(const mtts_conv_gemm_args *args, int32_t precision, int32_
  * (zeros for the other schedules). */
 int mtts_conv_gemm_plan(const mtts_conv_gemm_args *args, int32_t precision, int32_t tile_cfg, int32_t splits,
                         int32_t out[6]);
-/* Tests: out[0] = the schedule table's resident workgroups per CU of LDS-DMA schedule `schedule` (MTTS_GEMM_GLDS + i)
+/* Tests: out[0] = the schedule table's resident workgroups per CU of LDS-DMA schedule `schedule` (41 .. 47)
  * for an operand kind (0 fp32 A, 1 bf16 A, 2 / 3 the same with split weights, 4 three planes), out[1] = the runtime's
  * hipOccupancyMaxActiveBlocksPerMultiprocessor for that kernel (lean: its scalar-addressed variant). */
 int mtts_conv_gemm_glds_occupancy(int32_t schedule, int32_t kind, int32_t lean, int32_t out[2]);

@@ -905,93 +905,64 @@ int check_gather(const void *A, int lda, int cin, int ntaps, int K) {
 
 }  // namespace
 
-// Tile configurations: {WM, WN, TM, TN} -> BM x BN = 32*WM*TM x 32*WN*TN, 64*WM*WN threads.
+// Register-staged schedules: {WM, WN, TM, TN} -> BM x BN = 32*WM*TM x 32*WN*TN, 64*WM*WN threads.  The ids are
+// public (C ABI, tests, logs, profiles/) and keep the numbers of the tuning rounds' 19-entry table; only the
+// schedules a pick or a test runs are built, each for the precisions it runs at (the others: DESIGN.md §3).
 struct TileCfg {
-    int wm, wn, tm, tn, kb, depth = 1;  // depth: K steps in flight in registers (2: bf16 only)
+    int id, wm, wn, tm, tn, kb, depth;  // depth: K steps in flight in registers
+    bool bf16, f32;                     // built for
 };
 constexpr TileCfg kCfgs[] = {
-    {2, 2, 1, 2, 32},  // 0: 64 x 128, 256 thr (round-1 default)
-    {2, 2, 2, 2, 32},  // 1: 128 x 128, 256 thr
-    {1, 2, 1, 1, 32},  // 2: 32 x 64, 128 thr
-    {2, 2, 1, 1, 32},  // 3: 64 x 64, 256 thr
-    {1, 4, 1, 2, 32},  // 4: 32 x 256, 256 thr
-    {2, 4, 1, 2, 32},  // 5: 64 x 256, 512 thr
-    {1, 2, 1, 2, 32},  // 6: 32 x 128, 128 thr
-    {1, 4, 1, 1, 32},  // 7: 32 x 128, 256 thr (one 32x32 tile per wave)
-    {1, 4, 1, 1, 64},  // 8: config 7 with 64-wide K steps (bf16)
-    {2, 4, 1, 2, 64},  // 9: config 5 with 64-wide K steps (bf16)
-    {2, 2, 1, 2, 64},  // 10: config 0 with 64-wide K steps (bf16)
-    {1, 4, 1, 1, 32, 2},  // 11: config 7, two K steps in flight (bf16)
-    {1, 4, 1, 1, 64, 2},  // 12: config 8, two K steps in flight (bf16)
-    {2, 4, 1, 2, 64, 2},  // 13: config 9, two K steps in flight (bf16)
-    {2, 2, 1, 2, 64, 2},  // 14: 64 x 128, K64, two steps in flight (bf16)
-    {1, 4, 1, 2, 64, 2},  // 15: 32 x 256, K64, two steps in flight (bf16)
-    {2, 2, 1, 1, 64, 2},  // 16: 64 x 64, K64, two steps in flight (bf16)
-    {1, 2, 1, 1, 64, 2},  // 17: 32 x 64 (128 threads), K64, two steps in flight (bf16)
-    {2, 2, 1, 1, 32, 2},  // 18: config 3 (64 x 64, K32) with two steps in flight (fp32; bf16 too)
+    {3, 2, 2, 1, 1, 32, 1, false, true},   // 64 x 64, 256 thr
+    {7, 1, 4, 1, 1, 32, 1, true, true},    // 32 x 128, 256 thr (one 32x32 tile per wave)
+    {11, 1, 4, 1, 1, 32, 2, false, true},  // 7 with two K steps in flight
+    {12, 1, 4, 1, 1, 64, 2, true, false},  // 7 with 64-wide K steps, two in flight
+    {18, 2, 2, 1, 1, 32, 2, false, true},  // 3 with two K steps in flight
 };
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+constexpr TileCfg tile_cfg(int id) {
+    for (const TileCfg &c : kCfgs)
+        if (c.id == id) return c;
+    return {};
+}
 
 namespace mtts {
 // conv_gemm_glds.hip: sum part[0..S)[M][N] in split order + the epilogue (splitk_epilogue_kernel)
 int splitk_combine(const mtts_conv_gemm_args &p, int M, const float *part, int S, hipStream_t st);
 }
 
-template <bool BF16, int C, bool WS = false, bool AS = false>
+template <bool BF16, int ID, bool WS = false, bool AS = false>
 static void launch_cfg(const mtts_conv_gemm_args &p, int M, hipStream_t st, int splits = 1, float *part = nullptr) {
-    constexpr TileCfg c = kCfgs[C];
+    constexpr TileCfg c = tile_cfg(ID);
+    static_assert(BF16 ? c.bf16 : c.f32, "a schedule built for this precision");
     constexpr int BM = 32 * c.wm * c.tm, BN = 32 * c.wn * c.tn;
-    constexpr int KBc = BF16 ? c.kb : kBK;
     // the split-K partial store stages through the kernel's Bs (as the vector epilogue): it must hold the waves'
     // 4 KiB images, else the launch stays unsplit
-    constexpr size_t kBsBytes = (size_t)2 * (WS ? 2 : 1) * (BN + 1) * (KBc + Stage<BF16>::PAD) * sizeof(typename Stage<BF16>::T);
+    constexpr size_t kBsBytes = (size_t)2 * (WS ? 2 : 1) * (BN + 1) * (c.kb + Stage<BF16>::PAD) * sizeof(typename Stage<BF16>::T);
     if (kBsBytes < (size_t)c.wm * c.wn * 4096) splits = 1;
-    const int nk = (p.K + KBc - 1) / KBc;
+    const int nk = (p.K + c.kb - 1) / c.kb;
     const int ksteps = splits > 1 ? (nk + splits - 1) / splits : nk;
     const int S = splits > 1 ? (nk + ksteps - 1) / ksteps : 1;  // every split non-empty
     dim3 grid((unsigned)(((M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * S));
-    hipLaunchKernelGGL((conv_gemm_kernel<BF16, c.wm, c.wn, c.tm, c.tn, KBc, c.depth, WS, AS>),
+    hipLaunchKernelGGL((conv_gemm_kernel<BF16, c.wm, c.wn, c.tm, c.tn, c.kb, c.depth, WS, AS>),
                        grid, dim3(64 * c.wm * c.wn), 0, st, p, ksteps, S > 1 ? part : nullptr);
     if (S > 1) mtts::splitk_combine(p, M, part, S, st);
 }
 
-// Split-weight (MTTS_GEMM_F_W_SPLIT) register schedules: the two the heuristic picks, 7 (32-wide K steps)
-// and 12 (64-wide, two in flight); every other id runs the one with its K step width.  With
-// MTTS_GEMM_F_A_SPLIT the same two with the A residual plane (bf16x3).
-static void launch_ws(int id, const mtts_conv_gemm_args &p, int M, hipStream_t st) {
-    const bool as = p.flags & MTTS_GEMM_F_A_SPLIT;
-    if (kCfgs[id].kb == 64) {
-        if (as) launch_cfg<true, 12, true, true>(p, M, st);
-        else launch_cfg<true, 12, true>(p, M, st);
-    } else {
-        if (as) launch_cfg<true, 7, true, true>(p, M, st);
-        else launch_cfg<true, 7, true>(p, M, st);
-    }
+// bf16: 7 (32-wide K steps) or 12 (64-wide, two in flight), one weight plane, split weight planes
+// (MTTS_GEMM_F_W_SPLIT) or split weights and a split A (MTTS_GEMM_F_A_SPLIT, bf16x3); no split K
+template <int ID>
+static void launch_bf16(const mtts_conv_gemm_args &p, int M, hipStream_t st) {
+    if (!(p.flags & MTTS_GEMM_F_W_SPLIT)) launch_cfg<true, ID>(p, M, st);
+    else if (p.flags & MTTS_GEMM_F_A_SPLIT) launch_cfg<true, ID, true, true>(p, M, st);
+    else launch_cfg<true, ID, true>(p, M, st);
 }
 
-template <bool BF16>
-static void launch_by_id(int id, const mtts_conv_gemm_args &p, int M, hipStream_t st, int splits = 1, float *part = nullptr) {
-    if (BF16) splits = 1;  // split-K on the register schedules: fp32 only
+static void launch_f32(int id, const mtts_conv_gemm_args &p, int M, hipStream_t st, int splits, float *part) {
     switch (id) {
-        case 0: launch_cfg<BF16, 0>(p, M, st, splits, part); break;
-        case 1: launch_cfg<BF16, 1>(p, M, st, splits, part); break;
-        case 2: launch_cfg<BF16, 2>(p, M, st, splits, part); break;
-        case 3: launch_cfg<BF16, 3>(p, M, st, splits, part); break;
-        case 4: launch_cfg<BF16, 4>(p, M, st, splits, part); break;
-        case 5: launch_cfg<BF16, 5>(p, M, st, splits, part); break;
-        case 6: launch_cfg<BF16, 6>(p, M, st, splits, part); break;
-        case 7: launch_cfg<BF16, 7>(p, M, st, splits, part); break;
-        case 8: launch_cfg<BF16, 8>(p, M, st, splits, part); break;
-        case 9: launch_cfg<BF16, 9>(p, M, st, splits, part); break;
-        case 10: launch_cfg<BF16, 10>(p, M, st, splits, part); break;
-        case 11: launch_cfg<BF16, 11>(p, M, st, splits, part); break;
-        case 12: launch_cfg<BF16, 12>(p, M, st, splits, part); break;
-        case 13: launch_cfg<BF16, 13>(p, M, st, splits, part); break;
-        case 14: launch_cfg<BF16, 14>(p, M, st, splits, part); break;
-        case 15: launch_cfg<BF16, 15>(p, M, st, splits, part); break;
-        case 16: launch_cfg<BF16, 16>(p, M, st, splits, part); break;
-        case 17: launch_cfg<BF16, 17>(p, M, st, splits, part); break;
-        default: launch_cfg<BF16, 18>(p, M, st, splits, part); break;
+        case 3: launch_cfg<false, 3>(p, M, st, splits, part); break;
+        case 7: launch_cfg<false, 7>(p, M, st, splits, part); break;
+        case 11: launch_cfg<false, 11>(p, M, st, splits, part); break;
+        default: launch_cfg<false, 18>(p, M, st, splits, part); break;
     }
 }
 
@@ -1051,8 +1022,8 @@ static GldsRounds glds_rounds(const mtts_conv_gemm_args &p, int M, int id, int s
 // on 44 in the step's kernel trace (they share the chip with the weight-gradient stream) although 46 wins isolated
 // (10.6 vs 12.1 us); keeping 44 there moved the step by nothing (7.069 / 7.100 / 7.107 ms vs 7.102 / 7.080 / 7.130).
 static int pick_glds_rounds(const mtts_conv_gemm_args &p, int M) {
-    static const int kPickable[] = {14, 15, 9, 10, 12, 13};  // 46 47 (160-row tiles) | 41 42 44 45
-    if (!(p.flags & (MTTS_GEMM_F_A_BF16 | MTTS_GEMM_F_W_SPLIT)) && glds_tiles(p, M) > 256) return MTTS_GEMM_GLDS + 13;
+    static const int kPickable[] = {46, 47, 41, 42, 44, 45};  // the 160-row tiles first
+    if (!(p.flags & (MTTS_GEMM_F_A_BF16 | MTTS_GEMM_F_W_SPLIT)) && glds_tiles(p, M) > 256) return 45;
     int best = -1;
     double best_us = 0.;
     for (int id : kPickable) {
@@ -1061,7 +1032,7 @@ static int pick_glds_rounds(const mtts_conv_gemm_args &p, int M) {
         if (r.resident < 1) continue;
         if (best < 0 || r.us < best_us) best = id, best_us = r.us;
     }
-    return MTTS_GEMM_GLDS + best;
+    return best;
 }
 
 static int pick_cfg(const mtts_conv_gemm_args &p, int M, bool bf16) {
@@ -1070,24 +1041,22 @@ static int pick_cfg(const mtts_conv_gemm_args &p, int M, bool bf16) {
     // 841 us per step with the split-K counts below); the decoder-sized fp32 GEMMs keep config 7
     // the decoder-sized fp32 GEMMs (32-true) take config 7 with two K steps in flight (config 11): same MFMAs in
     // the same order, 32-true step 16.70 -> 16.50 ms; on the 3840-row encoder GEMMs the two-step 64 x 64 config 18
-    // measured no faster (bf16-parity 8.17 vs 8.20 ms; profiles/r04/f32_depth2/).  MTTS_GEMM_F32_DEPTH2=1 / 0:
-    // two steps in flight everywhere / nowhere
-    static const int d2 = [] { const char *e = getenv("MTTS_GEMM_F32_DEPTH2"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-    if (!bf16) return M <= 8192 ? (d2 == 1 ? 18 : 3) : (d2 == 0 ? 7 : 11);
+    // measured no faster (bf16-parity 8.17 vs 8.20 ms; profiles/r04/f32_depth2/)
+    if (!bf16) return M <= 8192 ? 3 : 11;
     if (p.act == MTTS_ACT_GELU || p.act == MTTS_ACT_DGELU) return 7;
     if (mtts::conv_gemm_glds_applies(p) && p.K >= 768) {
         const int t = glds_tiles(p, M);
         // the split-K rule's schedule: long reductions on grids far below the CU count (pick_splits)
-        if (t < 128 && p.K >= 1536 && p.N % 4 == 0) return MTTS_GEMM_GLDS + 10;
+        if (t < 128 && p.K >= 1536 && p.N % 4 == 0) return 42;
         // scalar-addressed LDS-DMA loop (whole-tap K steps) from half a round of 64-row tiles up: the LDS-DMA
         // kernels beat the register schedules there (profiles/r02/gemm_lean: 29.0 vs 29.7, 44.9 vs 48.5, 34.6 vs
         // 38.3 us on the 19200-row convs; 17.4 vs 19.0 on the half-resolution ones); which one, by rounds
         if (t >= 128 && mtts::conv_gemm_glds_lean(p)) return pick_glds_rounds(p, M);
-        if (t >= 128 && t <= 256) return MTTS_GEMM_GLDS + 10;
+        if (t >= 128 && t <= 256) return 42;
     }
     if (p.K < 768 && p.N >= 512 && glds_tiles(p, M) >= 256 && mtts::conv_gemm_glds_applies(p) &&
         mtts::conv_gemm_glds_lean(p))
-        return MTTS_GEMM_GLDS + 9;  // the decoder's q|k|v projection: 35.1 vs 37.2 us (one workgroup per CU:
+        return 41;  // the decoder's q|k|v projection: 35.1 vs 37.2 us (one workgroup per CU:
                                     // not below one round of tiles -- the text encoder's 3840-row GEMMs)
     return p.K >= 384 ? 12 : 7;
 }
@@ -1096,9 +1065,9 @@ static int pick_cfg(const mtts_conv_gemm_args &p, int M, bool bf16) {
 // fill the chip, 64 x 64 three-stage below (profiles/r02/gemm_lean: 19.0 vs 21.0 us on the 19200 x 256 x 768 conv,
 // 13.2 vs 13.4 on the 9600-row conv)
 static int pick_cfg_a16(const mtts_conv_gemm_args &p, int M) {
-    if (p.act == MTTS_ACT_GELU || p.act == MTTS_ACT_DGELU) return MTTS_GEMM_GLDS + 12;
+    if (p.act == MTTS_ACT_GELU || p.act == MTTS_ACT_DGELU) return 44;
     if (mtts::conv_gemm_glds_lean(p)) return pick_glds_rounds(p, M);
-    return glds_tiles(p, M) >= 256 ? MTTS_GEMM_GLDS + 9 : MTTS_GEMM_GLDS + 12;
+    return glds_tiles(p, M) >= 256 ? 41 : 44;
 }
 
 // Split weight planes (MTTS_GEMM_F_W_SPLIT, the parity policy's decoder forward): W's bytes double, which moves
@@ -1116,10 +1085,9 @@ static int pick_cfg_ws(const mtts_conv_gemm_args &p, int M) {
 // Split-K (LDS-DMA schedules, heuristic pick only): grids below half the chip with >= 24 K steps
 // fp32 register schedule 7 (32 x 128): split K when its tiles fill under one round with >= 48 K steps of 32
 // (the text encoder's FFN down-projection, 3840 x 192 x 2304: 240 tiles x 72 steps, 86-98 us unsplit in the
-// parity policy's fp32 encoder forward, profiles/r04/fused_wgrad_sum/launches); MTTS_GEMM_F32_SPLITK=0: off
+// parity policy's fp32 encoder forward, profiles/r04/fused_wgrad_sum/launches)
 static int pick_splits_f32(const mtts_conv_gemm_args &p, int M, int cfg, int splits) {
-    static const bool off = [] { const char *e = getenv("MTTS_GEMM_F32_SPLITK"); return e && e[0] == '0'; }();
-    if (p.N % 4 || off || !mtts::gemm_epilogue_vec_ok(p)) return 1;  // the combine is float4
+    if (p.N % 4 || !mtts::gemm_epilogue_vec_ok(p)) return 1;  // the combine is float4
     if (splits > 0) return splits;  // explicit (sweeps): any register schedule
     const int nk = (p.K + kBK - 1) / kBK;
     if (cfg == 3 || cfg == 18) {  // 64 x 64: 4 splits from 28 K steps, 2 from 20 (sweep: 3840 x 192 x 2304 44 us at 4 vs 58 at
@@ -1146,7 +1114,7 @@ static int pick_splits(const mtts_conv_gemm_args &p, int M, int cfg, int splits,
     if (cfg < MTTS_GEMM_GLDS || p.N % 4) return 1;
     if (splits > 0) return splits;
     const int nk = (p.K + 63) / 64;
-    if (cfg != MTTS_GEMM_GLDS + 10 || glds_tiles(p, M) >= 128 || nk < 24) return 1;
+    if (cfg != 42 || glds_tiles(p, M) >= 128 || nk < 24) return 1;
     return 4;
 }
 
@@ -1170,32 +1138,49 @@ static GemmPlan plan_gemm(const mtts_conv_gemm_args &p, bool bf16, int cfg, int 
     return {cfg, splits, ws};
 }
 
-// The schedule a call runs: the operand-driven rewrites of an explicit or heuristic config (three weight planes,
-// split weight planes, bf16 A, split A).  Shared by the launch and mtts_conv_gemm_workspace_size, so the size
-// query plans the schedule -- and the split count -- that will run.  *rc: MTTS_OK or the error.
+// A schedule id this library runs at the precision: -1 (the heuristic), a register schedule built for it, an
+// LDS-DMA schedule or the weight-stationary one.
+static bool known_cfg(int cfg, bool bf16) {
+    if (cfg == -1 || cfg == MTTS_GEMM_WREG || mtts::conv_gemm_glds_has(cfg)) return true;
+    const TileCfg c = tile_cfg(cfg);
+    return cfg >= 0 && c.id == cfg && (bf16 ? c.bf16 : c.f32);
+}
+
+// The schedule a call runs: an explicit id checked against what is built and what the operands allow, then the
+// operand-driven rewrites of an explicit or heuristic config (three weight planes, split weight planes, bf16 A,
+// split A).  Shared by the launch, mtts_conv_gemm_workspace_size and mtts_conv_gemm_plan, so the queries plan the
+// schedule -- and the split count -- that will run and refuse what the launch refuses.  *rc: MTTS_OK
+// or the error.
 static int resolve_cfg(const mtts_conv_gemm_args &p, bool bf16, int cfg, int M, int *rc) {
     *rc = MTTS_OK;
     auto err = [&](int code, const char *msg) {
         *rc = mtts::fail(code, msg);
         return cfg;
     };
+    if (!known_cfg(cfg, bf16)) return err(MTTS_ERR_INVALID_ARG, "conv_gemm: bad tile config");
+    if (cfg == MTTS_GEMM_WREG) {
+        if (!bf16 || !mtts::conv_gemm_wreg_applies(p))
+            return err(MTTS_ERR_UNSUPPORTED,
+                       "conv_gemm: weight-stationary schedule needs bf16, one stride-1 tap, K in {80,160,192,256}");
+        return cfg;
+    }
+    if (cfg >= MTTS_GEMM_GLDS && (!bf16 || !mtts::conv_gemm_glds_applies(p)))
+        return err(MTTS_ERR_UNSUPPORTED, "conv_gemm: LDS-DMA schedule needs bf16, cin >= 64 and a 0/1 a_scale");
     if (p.flags & MTTS_GEMM_F_SPLIT3) {  // bf16x6: LDS-DMA 64 x 64 (fp32 A split in the kernel)
         if (!bf16 || (p.flags & (MTTS_GEMM_F_A_BF16 | MTTS_GEMM_F_W_SPLIT | MTTS_GEMM_F_A_SPLIT)))
             return err(MTTS_ERR_INVALID_ARG, "conv_gemm: three weight planes need bf16 precision and an fp32 A");
         if (!mtts::conv_gemm_glds_applies(p))
             return err(MTTS_ERR_UNSUPPORTED, "conv_gemm: three weight planes need the LDS-DMA schedules (cin >= 64)");
-        if (cfg < 0) cfg = MTTS_GEMM_GLDS + 12;
+        if (cfg < 0) cfg = 44;
         if (cfg < MTTS_GEMM_GLDS) return err(MTTS_ERR_UNSUPPORTED, "conv_gemm: three weight planes need an LDS-DMA schedule");
     }
     // the weight-stationary kernel where its row streams get >= 2 tiles each (or the grid is one round):
     // the K <= 256 linears -- FF up-projection and its GELU' dgrad, q|k|v, the 19200-row projections
     // (tools/r5/gemm_replay.py, profiles/r05/wreg/)
-    static const bool wreg_pick = [] { const char *e = getenv("MTTS_GEMM_WREG_PICK"); return !(e && e[0] == '0'); }();
-    if (cfg < 0 && bf16 && wreg_pick && mtts::conv_gemm_wreg_applies(p) && mtts::conv_gemm_wreg_preferred(p, M))
+    if (cfg < 0 && bf16 && mtts::conv_gemm_wreg_applies(p) && mtts::conv_gemm_wreg_preferred(p, M))
         return MTTS_GEMM_WREG;
-    static const bool ws_pick = [] { const char *e = getenv("MTTS_GEMM_WS_PICK"); return !(e && e[0] == '0'); }();
     // (a bf16 A goes to the LDS-DMA pick below: pick_cfg_ws may answer a register-staged schedule)
-    if (cfg < 0 && bf16 && ws_pick && (p.flags & MTTS_GEMM_F_W_SPLIT) &&
+    if (cfg < 0 && bf16 && (p.flags & MTTS_GEMM_F_W_SPLIT) &&
         !(p.flags & (MTTS_GEMM_F_A_SPLIT | MTTS_GEMM_F_A_BF16)))
         cfg = pick_cfg_ws(p, M);
     if (p.flags & MTTS_GEMM_F_A_BF16) {  // bf16 A operands exist only in the LDS-DMA kernels
@@ -1221,14 +1206,14 @@ static int launch_plan(const mtts_conv_gemm_args &p, bool bf16, const GemmPlan &
     if (pl.cfg >= MTTS_GEMM_GLDS) {
         int s = pl.splits;
         if (pl.ws > 0 && (!ws || ws_bytes < pl.ws || (uintptr_t)ws % 16)) s = 1;  // no workspace: unsplit
-        return mtts::conv_gemm_glds_launch(pl.cfg - MTTS_GEMM_GLDS, p, M, s, static_cast<float *>(ws), st);
+        return mtts::conv_gemm_glds_launch(pl.cfg, p, M, s, static_cast<float *>(ws), st);
     }
-    if (bf16 && (p.flags & MTTS_GEMM_F_W_SPLIT)) launch_ws(pl.cfg, p, M, st);
-    else if (bf16) launch_by_id<true>(pl.cfg, p, M, st);
+    if (bf16 && pl.cfg == 12) launch_bf16<12>(p, M, st);
+    else if (bf16) launch_bf16<7>(p, M, st);
     else {
         int s = pl.splits;
         if (pl.ws == 0 || !ws || ws_bytes < pl.ws || (uintptr_t)ws % 16) s = 1;  // no workspace: unsplit
-        launch_by_id<false>(pl.cfg, p, M, st, s, static_cast<float *>(ws));
+        launch_f32(pl.cfg, p, M, st, s, static_cast<float *>(ws));
     }
     return mtts::check_launch("conv_gemm_kernel");
 }
@@ -1256,23 +1241,12 @@ static int conv_gemm_impl(const mtts_conv_gemm_args *args, int32_t precision, in
     MTTS_CHECK_ARG(!(p.flags & MTTS_GEMM_F_A_SPLIT) ||
                        ((p.flags & MTTS_GEMM_F_W_SPLIT) && !(p.flags & MTTS_GEMM_F_A_BF16)),
                    "conv_gemm: a split A needs split weight planes and an fp32 A");
-    const bool glds_id = cfg >= MTTS_GEMM_GLDS && cfg < MTTS_GEMM_GLDS + mtts::conv_gemm_glds_num_cfgs();
-    const bool wreg_id = cfg == MTTS_GEMM_WREG;
-    MTTS_CHECK_ARG((cfg >= -1 && cfg < kNumCfgs) || glds_id || wreg_id,
-                   "conv_gemm: bad tile config");
+    const bool bf16 = precision == MTTS_PREC_BF16;
+    MTTS_CHECK_ARG(known_cfg(cfg, bf16), "conv_gemm: bad tile config");
     MTTS_CHECK_ARG(splits >= 0, "conv_gemm: bad split count");
     const int M = p.nb * p.To;
     if (M == 0) return MTTS_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const bool bf16 = precision == MTTS_PREC_BF16;
-    if (wreg_id) {  // weight-stationary schedule, explicit id
-        if (!bf16 || !mtts::conv_gemm_wreg_applies(p))
-            return mtts::fail(MTTS_ERR_UNSUPPORTED,
-                              "conv_gemm: weight-stationary schedule needs bf16, one stride-1 tap, K in {80,160,192,256}");
-        return mtts::conv_gemm_wreg_launch(p, M, st);
-    }
-    if (glds_id && (!bf16 || !mtts::conv_gemm_glds_applies(p)))
-        return mtts::fail(MTTS_ERR_UNSUPPORTED, "conv_gemm: LDS-DMA schedule needs bf16, cin >= 64 and a 0/1 a_scale");
     cfg = resolve_cfg(p, bf16, cfg, M, &rc);
     if (rc) return rc;
     const GemmPlan pl = plan_gemm(p, bf16, cfg, splits);
@@ -1329,7 +1303,7 @@ extern "C" int mtts_conv_gemm_plan(const mtts_conv_gemm_args *args, int32_t prec
     int s = pl.splits;
     if (pl.cfg >= MTTS_GEMM_GLDS && pl.cfg < MTTS_GEMM_WREG) {
         if (pl.ws == 0) s = 1;
-        r = glds_rounds(*args, M, pl.cfg - MTTS_GEMM_GLDS, s);
+        r = glds_rounds(*args, M, pl.cfg, s);
         if (s > 1) s = (int)(pl.ws / ((size_t)M * args->N * sizeof(float)));  // every split non-empty
     }
     out[0] = pl.cfg, out[1] = s, out[2] = r.tiles, out[3] = r.resident, out[4] = r.rounds, out[5] = r.fill_pm;

@@ -539,6 +539,7 @@ inline int kind_of(const mtts_conv_gemm_args &p) {
 }
 
 struct GldsCfg {
+    int id;  // the public schedule id (MTTS_GEMM_GLDS + its place in the tuning rounds' table: DESIGN.md §3)
     int wm, wn, tm, tn, stages;
     unsigned kinds;  // operand kinds with an instantiation (LDS <= 160 KiB, registers)
     bool lean_only = false;  // only the scalar-addressed loop is built (the register-addressed one spills)
@@ -564,41 +565,30 @@ struct GldsCfg {
 // two-stage 46 on every 9600-row shape, 3-27 % on the 19200-row ones) and 160 x 32 with three stages for fp32 A
 // (five waves, 1.7-2x slower than 46: ten DMA instructions per wave and step).
 constexpr GldsCfg kGlds[] = {
-    {1, 4, 2, 2, 2, kF32},   // 32: 64 x 256, 256 thr, 2 stages (96 KiB)
-    {1, 4, 2, 2, 3, 0},      // 33: 64 x 256, 3 stages (144 KiB; fp32 A spills: 7x slower)
-    {2, 2, 2, 2, 2, kF32},   // 34: 128 x 128, 2 stages (96 KiB)
-    {2, 2, 2, 2, 3, 0},      // 35: 128 x 128, 3 stages (144 KiB; fp32 A spills: 7x slower)
-    {1, 4, 1, 2, 2, kF32},   // 36: 32 x 256, 2 stages (80 KiB)
-    {1, 4, 1, 2, 3, kF32},   // 37: 32 x 256, 3 stages (120 KiB)
-    {2, 2, 1, 2, 2, kF32},   // 38: 64 x 128, 2 stages (64 KiB)
-    {2, 2, 1, 2, 3, kF32},   // 39: 64 x 128, 3 stages (96 KiB)
-    {1, 4, 1, 1, 3, kF32},   // 40: 32 x 128, 3 stages (72 KiB)
-    {2, 4, 1, 2, 2, kF32 | kB16 | kF32WS | kB16WS},  // 41: 64 x 256, 512 thr (waves 32 x 64), 2 stages (96 KiB; split
-                                                      // W: 144 KiB with bf16 A, 160 KiB with fp32 A)
-    {2, 4, 1, 2, 3, kF32 | kB16},                     // 42: 64 x 256, 512 thr, 3 stages (144 KiB)
-    {1, 2, 2, 2, 3, kF32},                            // 43: 64 x 128, 128 thr (waves 64 x 64), 3 stages (96 KiB)
-    {2, 2, 1, 1, 3, kF32 | kB16 | kF32WS | kB16WS | kX3},  // 44: 64 x 64, 3 stages (72 KiB; bf16x6: 120 KiB)
-    {2, 2, 1, 1, 2, kF32 | kF32WS | kX3},             // 45: 64 x 64, 2 stages (48 KiB)
-    {5, 2, 1, 1, 2, kF32 | kB16 | kF32WS | kB16WS},   // 46: 160 x 64, 640 thr (waves 32 x 32), 2 stages
-    {5, 2, 1, 2, 3, kB16 | kB16WS, true},             // 47: 160 x 128, 640 thr (waves 32 x 64), 3 stages
+    {41, 2, 4, 1, 2, 2, kF32 | kB16 | kF32WS | kB16WS},  // 64 x 256, 512 thr (waves 32 x 64), 2 stages (96 KiB; split
+                                                          // W: 144 KiB with bf16 A, 160 KiB with fp32 A)
+    {42, 2, 4, 1, 2, 3, kF32 | kB16},                     // 64 x 256, 512 thr, 3 stages (144 KiB)
+    {44, 2, 2, 1, 1, 3, kF32 | kB16 | kF32WS | kB16WS | kX3},  // 64 x 64, 3 stages (72 KiB; bf16x6: 120 KiB)
+    {45, 2, 2, 1, 1, 2, kF32 | kF32WS | kX3},             // 64 x 64, 2 stages (48 KiB)
+    {46, 5, 2, 1, 1, 2, kF32 | kB16 | kF32WS | kB16WS},   // 160 x 64, 640 thr (waves 32 x 32), 2 stages
+    {47, 5, 2, 1, 2, 3, kB16 | kB16WS, true},             // 160 x 128, 640 thr (waves 32 x 64), 3 stages
 };
 constexpr int kNumGlds = sizeof(kGlds) / sizeof(kGlds[0]);
+// The table index of public schedule id (-1: none).  Everything below the mtts:: interface works on indices.
+constexpr int glds_ix(int id) {
+    for (int c = 0; c < kNumGlds; ++c)
+        if (kGlds[c].id == id) return c;
+    return -1;
+}
 
-// The instantiation schedule c runs for an operand kind: its own where it has one; else, as before the table,
+// The instantiation schedule c runs for an operand kind: its own where it has one (47: for whole-tap K steps); else
 //  * three planes (bf16x6): 64 x 64 three-stage (44) or two-stage (45) by the schedule's stage count;
-//  * split weights: 64 x 256 two-stage (41) for tiles >= 128 wide, else 64 x 64 three- (44) / two-stage (45; bf16 A:
-//    41) by the stage count (a 128 x 128 two-stage split-weight instance, round 4, ran 3-5x slower than the 64-row
-//    ones on the FFN up-projection -- profiles/r04/sweeps/ff1_probe.txt -- and was removed);
-//  * one plane: 64 x 256 two-stage (41).
+//  * one or two planes: 64 x 256 two-stage (41), the one schedule with all four kinds.
 constexpr int glds_run_id(int c, int kind, bool lean = true) {
-    if (kGlds[c].lean_only && !lean) return 9;
+    if (kGlds[c].lean_only && !lean) return glds_ix(41);
     if (kGlds[c].kinds & (1u << kind)) return c;
-    if (kind == 4) return kGlds[c].stages >= 3 ? 12 : 13;
-    if (kind >= 2) {
-        const int w = kGlds[c].wn * kGlds[c].tn * 32 >= 128 ? 9 : (kGlds[c].stages == 2 ? 13 : 12);
-        return (kGlds[w].kinds & (1u << kind)) ? w : 9;
-    }
-    return 9;
+    if (kind == 4) return glds_ix(kGlds[c].stages >= 3 ? 44 : 45);
+    return glds_ix(41);
 }
 constexpr int glds_bm(int c) { return 32 * kGlds[c].wm * kGlds[c].tm; }
 constexpr int glds_bn(int c) { return 32 * kGlds[c].wn * kGlds[c].tn; }
@@ -608,7 +598,7 @@ constexpr int glds_stage_bytes(int c, int kind) {
 constexpr int glds_resident(int c, int kind, bool lean = true) {
     // the one instantiation whose registers bind: 41 with a bf16 A and one plane, register-addressed loop -- 140 VGPRs,
     // three waves per SIMD, one 8-wave workgroup (80 KiB of LDS would admit two; its scalar-addressed loop: 108, two)
-    if (c == 9 && kind == 1 && !lean) return 1;
+    if (c == glds_ix(41) && kind == 1 && !lean) return 1;
     const int lds = kGlds[c].stages * glds_stage_bytes(c, kind), nt = 64 * kGlds[c].wm * kGlds[c].wn;
     const int by_lds = 160 * 1024 / lds, by_thr = 2048 / nt;
     return by_lds < by_thr ? by_lds : by_thr;
@@ -619,12 +609,8 @@ constexpr int glds_resident(int c, int kind, bool lean = true) {
 namespace mtts {
 // The LEAN loop needs whole-tap K steps and 32-bit byte offsets with room for MTTS_GLDS_OOB.
 bool conv_gemm_glds_lean(const mtts_conv_gemm_args &p) {
-    static const bool off = [] {
-        const char *e = getenv("MTTS_GLDS_LEAN");
-        return e && e[0] == '0';
-    }();
     const int es = (p.flags & MTTS_GEMM_F_A_BF16) ? 2 : 4;
-    return !off && p.cin % kBK == 0 && (long long)p.nb * p.Ti * p.lda * es < (1ll << 31) &&
+    return p.cin % kBK == 0 && (long long)p.nb * p.Ti * p.lda * es < (1ll << 31) &&
            (long long)p.N * p.Kp * 2 < (1ll << 31);
 }
 }  // namespace mtts
@@ -665,7 +651,7 @@ int launch_glds_t(const mtts_conv_gemm_args &p, int M, int splits, float *part, 
 template <int C>
 int launch_glds(const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
     if constexpr (kGlds[C].lean_only) {
-        if (!mtts::conv_gemm_glds_lean(p)) return launch_glds<9>(p, M, splits, part, st);
+        if (!mtts::conv_gemm_glds_lean(p)) return launch_glds<glds_ix(41)>(p, M, splits, part, st);
     }
     switch (kind_of(p)) {
         case 4: return launch_glds_t<glds_run_id(C, 4), 4>(p, M, splits, part, st);
@@ -700,17 +686,17 @@ int occupancy_glds(int kind, bool lean) {
 }
 
 template <int... I>
-int occupancy_glds_id(int id, int kind, bool lean, std::integer_sequence<int, I...>) {
+int occupancy_glds_ix(int c, int kind, bool lean, std::integer_sequence<int, I...>) {
     int n = -1;
-    ((id == I ? (n = occupancy_glds<I>(kind, lean), true) : false) || ...);
+    ((c == I ? (n = occupancy_glds<I>(kind, lean), true) : false) || ...);
     return n;
 }
 
 template <int... I>
-int launch_glds_id(int id, const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st,
+int launch_glds_ix(int c, const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st,
                    std::integer_sequence<int, I...>) {
     int rc = MTTS_ERR_INVALID_ARG;
-    ((id == I ? (rc = launch_glds<I>(p, M, splits, part, st), true) : false) || ...);
+    ((c == I ? (rc = launch_glds<I>(p, M, splits, part, st), true) : false) || ...);
     return rc;
 }
 
@@ -718,7 +704,7 @@ int launch_glds_id(int id, const mtts_conv_gemm_args &p, int M, int splits, floa
 
 namespace mtts {
 
-int conv_gemm_glds_num_cfgs() { return kNumGlds; }
+bool conv_gemm_glds_has(int id) { return glds_ix(id) >= 0; }
 
 // Whether the LDS-DMA kernels can run this GEMM (bf16; 16-byte aligned rows; 0/1 row mask or none;
 // 32-bit element offsets).
@@ -746,7 +732,7 @@ int splitk_combine(const mtts_conv_gemm_args &p, int M, const float *part, int S
 }
 
 int conv_gemm_glds_launch(int id, const mtts_conv_gemm_args &p, int M, int splits, float *part, hipStream_t st) {
-    return launch_glds_id(id, p, M, splits, part, st, std::make_integer_sequence<int, kNumGlds>{});
+    return launch_glds_ix(glds_ix(id), p, M, splits, part, st, std::make_integer_sequence<int, kNumGlds>{});
 }
 
 // The tile, stage bytes and resident workgroups per CU of the instantiation that schedule `id` runs for p's
@@ -754,15 +740,16 @@ int conv_gemm_glds_launch(int id, const mtts_conv_gemm_args &p, int M, int split
 GldsInfo conv_gemm_glds_info(int id, const mtts_conv_gemm_args &p) {
     const int kind = kind_of(p);
     GldsInfo g = {};
-    if (id < 0 || id >= kNumGlds) return g;
-    const int r = glds_run_id(id, kind, conv_gemm_glds_lean(p));
-    g.run_id = r;
+    const int c = glds_ix(id);
+    if (c < 0) return g;
+    const int r = glds_run_id(c, kind, conv_gemm_glds_lean(p));
+    g.run_id = kGlds[r].id;
     g.bm = glds_bm(r);
     g.bn = glds_bn(r);
     g.stages = kGlds[r].stages;
     g.stage_bytes = glds_stage_bytes(r, kind);
     g.resident = glds_resident(r, kind, conv_gemm_glds_lean(p));
-    g.own = r == id;
+    g.own = r == c;
     return g;
 }
 }  // namespace mtts
@@ -771,12 +758,12 @@ GldsInfo conv_gemm_glds_info(int id, const mtts_conv_gemm_args &p) {
 // CU, out[1] = hipOccupancyMaxActiveBlocksPerMultiprocessor.  kind: 0 fp32 A, 1 bf16 A, 2 / 3 the same with split
 // weights, 4 three planes.  MTTS_ERR_INVALID_ARG when the schedule has no instantiation of its own for the kind.
 extern "C" int mtts_conv_gemm_glds_occupancy(int32_t schedule, int32_t kind, int32_t lean, int32_t out[2]) {
-    const int id = schedule - MTTS_GEMM_GLDS;
-    MTTS_CHECK_ARG(out && id >= 0 && id < kNumGlds && kind >= 0 && kind < kNumKinds &&
-                       (kGlds[id].kinds & (1u << kind)) && (lean || !kGlds[id].lean_only),
+    const int c = glds_ix(schedule);
+    MTTS_CHECK_ARG(out && c >= 0 && kind >= 0 && kind < kNumKinds && (kGlds[c].kinds & (1u << kind)) &&
+                       (lean || !kGlds[c].lean_only),
                    "conv_gemm_glds_occupancy: no such instantiation");
-    out[0] = glds_resident(id, kind, lean != 0);
-    out[1] = occupancy_glds_id(id, kind, lean != 0, std::make_integer_sequence<int, kNumGlds>{});
+    out[0] = glds_resident(c, kind, lean != 0);
+    out[1] = occupancy_glds_ix(c, kind, lean != 0, std::make_integer_sequence<int, kNumGlds>{});
     if (out[1] < 0) return mtts::fail(MTTS_ERR_HIP, "conv_gemm_glds_occupancy: occupancy query failed");
     return MTTS_OK;
 }

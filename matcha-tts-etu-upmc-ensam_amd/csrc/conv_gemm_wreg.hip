@@ -167,10 +167,7 @@ WrGrid wreg_grid(const mtts_conv_gemm_args &p, int M) {
             n = pr.multiProcessorCount;
         return n;
     }();
-    static const int per_cu = [] {  // MTTS_WREG_WG_PER_CU: workgroups per CU of the grid (default 2)
-        const char *e = getenv("MTTS_WREG_WG_PER_CU");
-        return e && atoi(e) > 0 ? atoi(e) : 2;
-    }();
+    constexpr int per_cu = 2;  // workgroups per CU of the grid (WrGeom's LDS admits two)
     WrGrid g;
     g.ncg = (p.N + 32 * kNW - 1) / (32 * kNW);
     g.mtiles = (M + kBM - 1) / kBM;
@@ -190,8 +187,7 @@ int launch_wreg_e(const mtts_conv_gemm_args &p, int M, hipStream_t st) {
 template <bool ABF16, int NPL, int KS>
 int launch_wreg_t(const mtts_conv_gemm_args &p, int M, hipStream_t st) {
     const bool rm = p.a_scale != nullptr;
-    static const bool rt_only = [] { const char *e = getenv("MTTS_WREG_EK_RT"); return e && e[0] == '1'; }();
-    switch (rt_only ? (int)mtts::EK_RT : mtts::gemm_epilogue_kind(p)) {
+    switch (mtts::gemm_epilogue_kind(p)) {
         case mtts::EK_LIN_C16:
             return rm ? launch_wreg_e<ABF16, NPL, KS, mtts::EK_LIN_C16, true>(p, M, st)
                       : launch_wreg_e<ABF16, NPL, KS, mtts::EK_LIN_C16, false>(p, M, st);

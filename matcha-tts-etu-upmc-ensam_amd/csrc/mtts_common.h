@@ -46,8 +46,8 @@ __device__ __forceinline__ int tap_off(const P &p, int j) {
 
 struct mtts_conv_gemm_args;
 namespace mtts {
-// conv_gemm_glds.hip: bf16 LDS-DMA schedules (ids MTTS_GEMM_GLDS + 0 .. num - 1)
-int conv_gemm_glds_num_cfgs();
+// conv_gemm_glds.hip: bf16 LDS-DMA schedules, named by their public ids (41, 42, 44 .. 47)
+bool conv_gemm_glds_has(int id);
 bool conv_gemm_glds_applies(const mtts_conv_gemm_args &p);
 bool conv_gemm_glds_lean(const mtts_conv_gemm_args &p);  // whole-tap K steps: scalar-addressed loop
 // splits > 1: split-K into `part` (conv_gemm_glds_splitk_bytes of workspace) + a combine/epilogue pass

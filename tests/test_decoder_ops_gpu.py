@@ -341,11 +341,13 @@ def test_gemm_lds_dma_split_k_epilogue(cfg, splits, act, pre):
 
 
 @pytest.mark.parametrize("B,T,Cin,Cout,k,cfg", [(32, 600, 1024, 256, 1, -1), (32, 300, 256, 256, 3, -1),
-                                                 (5, 77, 256, 320, 3, 44), (4, 120, 192, 768, 3, 42)])
+                                                 (5, 77, 256, 320, 3, 44), (4, 120, 192, 768, 3, 42),
+                                                 (2, 33, 96, 64, 3, 41), (2, 33, 96, 64, 3, 42), (2, 33, 96, 64, 3, 44)])
 def test_bf16_operand_storage_bitwise(B, T, Cin, Cout, k, cfg):
     """bf16-stored A (MTTS_GEMM_F_A_BF16) and bf16 C (MTTS_GEMM_F_C_BF16): the GEMM and the wgrad on a
     bf16 A are bitwise equal to the fp32-A path on the same (bf16-representable) values, and a bf16 C
-    is the fp32 C rounded once."""
+    is the fp32 C rounded once.  (The 96-channel cases: K steps that cross taps, the register-addressed loop of
+    the 64-row LDS-DMA schedules for both A storages.)"""
     from matcha.models.components import _ops as O
 
     g = torch.Generator(device="cpu").manual_seed(B + T + Cin + Cout)

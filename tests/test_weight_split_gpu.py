@@ -89,13 +89,17 @@ def test_split_weight_packing_planes():
 
 @pytest.mark.parametrize("B,T,Cin,Cout,k,cfg", [(32, 120, 192, 192, 5, -1), (4, 120, 192, 576, 1, -1),
                                                 (8, 120, 768, 192, 3, -1), (8, 120, 192, 768, 3, 7),
-                                                (8, 120, 192, 768, 3, 12), (3, 37, 256, 80, 1, -1)])
+                                                (8, 120, 192, 768, 3, 12), (3, 37, 256, 80, 1, -1),
+                                                (2, 33, 64, 64, 3, 41), (2, 33, 64, 64, 3, 44),
+                                                (2, 33, 96, 64, 3, 41), (2, 33, 96, 64, 3, 44)])
 def test_split_a_bf16x3_vs_float64(B, T, Cin, Cout, k, cfg):
     """MTTS_GEMM_F_A_SPLIT (precise_forward): fp32 activations (NOT bf16-exact) and fp32 weights, both split
     into hi + lo bf16 planes, A_hi W_hi + A_hi W_lo + A_lo W_hi -- an fp32 GEMM to ~2^-16 of the operands
     (float64 reference); the one-A-plane result (bf16 activations) is far off, so the check has teeth.  The
     text encoder's shapes (M = 32 x 120: prenet k = 5, q|k|v, FFN k = 3 both ways, mean projection) on both
-    register schedules."""
+    register schedules.  An LDS-DMA id (41, 44) applies to the one-A-plane comparison call only -- fp32 A with
+    split weights on the scalar-addressed (64 channels) and register-addressed (96) loop; the split-A call then
+    takes the heuristic's register schedule."""
     from matcha.models.components import _ops as O
 
     g = torch.Generator().manual_seed(B * Cout + k)
@@ -195,13 +199,14 @@ def test_pack_three_planes_exact():
 @pytest.mark.parametrize("B,T,Cin,Cout,k,splits", [(32, 120, 192, 192, 5, 0), (4, 120, 192, 576, 1, 0),
                                                    (8, 120, 768, 192, 3, 0), (8, 120, 768, 192, 3, 1),
                                                    (8, 120, 192, 768, 3, 0), (3, 37, 256, 80, 1, 0),
-                                                   (32, 120, 256, 1, 1, 0)])
+                                                   (32, 120, 256, 1, 1, 0), (2, 33, 96, 64, 3, 0)])
 def test_bf16x6_vs_float64(B, T, Cin, Cout, k, splits):
     """MTTS_GEMM_F_SPLIT3 (precise_forward("bf16x6")): fp32 activations and weights each as three exact bf16
     planes, the six products of combined order <= 2^-16.  Measured 1.0-2.8x the exact-fp32 MFMA kernel's
     distance to float64 (~1e-7 .. 6e-7 relative): the omitted products are ~2^-23, but the six accumulation
     chains each round -- fp32-class, not bit-faithful; bound 4x.  The text encoder's shapes
-    (prenet k = 5, q|k|v, FFN k = 3 both ways with and without split-K, the mean and duration projections)."""
+    (prenet k = 5, q|k|v, FFN k = 3 both ways with and without split-K, the mean and duration projections), and
+    96 channels: K steps that cross taps (the register-addressed loop)."""
     from matcha.models.components import _ops as O
 
     g = torch.Generator().manual_seed(B * Cout + k + 7)
@@ -254,8 +259,9 @@ def test_precise_forward_bf16x6_encoder_close_to_32true():
                                                    (32, 120, 768, 192, 3, 4), (32, 120, 192, 576, 1, 0),
                                                    (3, 37, 256, 80, 1, 0), (32, 120, 192, 768, 3, 2)])
 def test_fp32_two_steps_in_flight_bitwise(B, T, Cin, Cout, k, splits):
-    """The exact-fp32 register schedules with two K steps in flight (configs 18 / 11, MTTS_GEMM_F32_DEPTH2) issue
-    the same MFMAs in the same order as configs 3 / 7: bitwise equal outputs, split-K included."""
+    """The exact-fp32 register schedules with two K steps in flight (configs 18 / 11; the heuristic takes 11 above
+    8192 rows, 18 only by explicit id) issue the same MFMAs in the same order as configs 3 / 7: bitwise equal
+    outputs, split-K included."""
     from matcha.models.components import _ops as O
 
     g = torch.Generator().manual_seed(B * Cout + k + 11)

@@ -31,7 +31,7 @@ variants = [
 for a_name, A in (("A32", A32),):
     for name, kw, C in variants:
         row = []
-        for cfg in (list(range(-1, 18)) + [41, 44] if a_name == "A32" else [-1, 41, 44]):
+        for cfg in ([-1, 7, 12, 41, 44] if a_name == "A32" else [-1, 41, 44]):
             run = lambda: O._gemm(A, M, M, 1, 1, [0], K, Wp, Kp, N, C, M, prec=P, tile_cfg=cfg, **kw)
             try:
                 run(); torch.cuda.synchronize()

@@ -29,7 +29,7 @@ def t_ev(fn, iters=20):
     return a.elapsed_time(b) / (3 * iters) * 1e3
 
 prec_name = sys.argv[1] if len(sys.argv) > 1 else "bf16"
-cfgs = [int(c) for c in sys.argv[2].split(",")] if len(sys.argv) > 2 else list(range(8))
+cfgs = [int(c) for c in sys.argv[2].split(",")] if len(sys.argv) > 2 else ([7, 12] if prec_name == "bf16" else [3, 7, 11, 18])
 prec = O.PREC_BF16 if prec_name == "bf16" else O.PREC_FP32
 shapes = [("conv3_full_256", 32, 600, 256, 256, 3), ("conv3_half_256", 32, 300, 256, 256, 3),
           ("conv3_half_512", 32, 300, 512, 256, 3), ("conv3_full_512", 32, 600, 512, 256, 3),

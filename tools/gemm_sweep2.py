@@ -37,7 +37,7 @@ SHAPES = [
     ("ff1_full", 32, 600, 256, 1, 1024, 1, 1, 0, 0, 0), ("ff2d_full", 32, 600, 256, 1, 1024, 2, 1, 0, 0, 0),
     ("dec_full_k3", 32, 600, 256, 3, 256, 0, 0, 0, 1, 0), ("ff2_full", 32, 600, 1024, 1, 256, 0, 0, 1, 0, 0),
 ]
-cands = [(-1, 0), (7, 1), (12, 1), (41, 1), (42, 1), (38, 1), (44, 1), (45, 1), (41, 2), (42, 2), (44, 2), (42, 4),
+cands = [(-1, 0), (7, 1), (12, 1), (41, 1), (42, 1), (44, 1), (45, 1), (41, 2), (42, 2), (44, 2), (42, 4),
          (44, 4)]
 only = sys.argv[2].split(",") if len(sys.argv) > 2 else None
 if only:

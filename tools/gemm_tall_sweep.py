@@ -39,7 +39,7 @@ for name, B, T, cin, k, N, res, msk, act in SHAPES:
         ref = ref + r
     for a16 in (False, True):
         x = x32.to(torch.bfloat16) if a16 else x32
-        cands = [-1] + list(range(32, 55)) + ([] if a16 else [7, 12])
+        cands = [-1, 41, 42, 44, 45, 46, 47] + ([] if a16 else [7, 12])
         res_t = {}
         for cfg in cands:
             run = lambda: O._gemm(x, T, T, B, 1, offs, cin, Wp, Kp, N, y, T, prec=P, a_scale=m, bias=bias,

@@ -36,7 +36,7 @@ for split in (False, True):
     Wp, Kp = planes[split]
     for name, kw, C in variants:
         row = []
-        for cfg in [-1, 0, 1, 3, 5, 7, 12, 32, 34, 36, 38, 41, 44, 45]:
+        for cfg in [-1, 7, 12, 41, 44, 45]:
             run = lambda: O._gemm(A, M, M, 1, 1, [0], K, Wp, Kp, N, C, M, prec=P, tile_cfg=cfg, **kw)  # noqa: E731
             try:
                 run()
