@@ -15,6 +15,8 @@
  *   mtts_maximum_path_f32          <- matcha/utils/monotonic_align/__init__.py:40-55  maximum_path(value, mask)
  *   mtts_prior_maximum_path        <- matcha/models/matcha_tts.py:276-288 (log-prior lattice + maximum_path +
  *                                     the duration target), fused
+ *   mtts_duration_path             <- matcha/models/matcha_tts.py:273-274 + utils/model.py:77-114 (the alignment
+ *                                     from precomputed durations, use_precomputed_durations=True)
  *   mtts_expand_rows_fwd / _bwd    <- matcha/models/matcha_tts.py:314-315  mu_y = attn^T @ mu_x
  *   mtts_segment_crop_fwd / _bwd   <- matcha/models/matcha_tts.py:290-315  forward(out_size=...): random mel segment
  *   mtts_compute_batch_alignments  <- matcha/utils/monotonic_align/core.pyx:101-128   compute_batch_alignments(...)
@@ -120,6 +122,27 @@ int mtts_prior_maximum_path(const float *mu_x, const float *y, const int64_t *x_
                             int32_t B, int32_t C, int32_t Tx, int32_t Ty, float *path, int32_t *lengths_out,
                             int32_t *row_start_out, float *dur_out, int32_t *col_row_out, float *lattice_out,
                             void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
+ * Alignment from precomputed durations (matcha_tts.py:273-274: generate_path(durations, x_mask * y_mask) and its
+ * sum(-1); utils/model.py:77-114), as the run-length alignment the consumers below read.  Per utterance b:
+ *   t_x = clamp(x_lengths[b], 0, Tx), t_y = clamp(y_lengths[b], 0, Ty)            (int64 [B], device)
+ *   c_0 = 0, c_{x+1} = c_x + max(durations[b,x], 0)   in float64 (exact on fp32 terms; NaN counts as 0)
+ *   e_x = (int)min(ceil(c_x), t_y)
+ *   row_start[b,x] = e_x, dur[b,x] = e_{x+1} - e_x    for x < t_x; -1 and 0 past t_x
+ *   t_cov = e_{t_x}: the frames the durations cover (<= t_y; they need not add up to t_y)
+ *   col_row[b,y] = the x < t_x with e_x <= y < e_{x+1} for y < t_cov, else -1
+ *   path[b,x,y] = (col_row[b,y] == x)                 float32 [B,Tx,Ty], optional, fully written
+ *   lengths_out = (t_x, t_y), run_lengths_out = (t_x, t_cov)                      int32 [B,2]
+ * durations float32 [B,Tx]; every output is optional, but `path` needs row_start_out and run_lengths_out (it is
+ * written from them).  Give run_lengths to mtts_expand_rows_bwd / mtts_segment_crop_bwd as their `lengths` (the
+ * last row's run ends at t_cov, and a row of length 0 has row_start[x] == row_start[x+1]) and lengths to
+ * mtts_segment_crop_fwd (the window is drawn on t_y, as the reference crops on y_lengths).  No workspace, no
+ * atomics, fixed order.  MTTS_ERR_SHAPE for Tx > MTTS_MAS_MAX_TX or B > 65535.
+ */
+int mtts_duration_path(const float *durations, const int64_t *x_lengths, const int64_t *y_lengths, int32_t B,
+                       int32_t Tx, int32_t Ty, float *path, int32_t *lengths_out, int32_t *run_lengths_out,
+                       int32_t *row_start_out, float *dur_out, int32_t *col_row_out, void *hip_stream);
 
 /*
  * mu_y = attn^T @ mu_x for a hard alignment (matcha_tts.py:314-315) as a gather, and its backward:

@@ -1167,6 +1167,96 @@ __global__ __launch_bounds__(256) void mas_runs_kernel(const int32_t *__restrict
     }
 }
 
+// Precomputed durations to the run-length alignment mas_runs_kernel's consumers read (matcha_tts.py:273-274:
+// generate_path(durations, x_mask * y_mask) and its sum(-1), model.py:77-114, restated on runs -- the dense
+// [B,Tx,Ty] mask and its elementwise passes are never formed).  One 256-thread block per utterance:
+//   c_0 = 0, c_{x+1} = c_x + max(d[x], 0) in float64 (NaN adds 0; rows >= t_x add 0), e_x = min(ceil(c_x), t_y)
+//   row x < t_x covers the frames [e_x, e_{x+1}); t_cov = e_{t_x} <= t_y frames are covered
+// (generate_path's row x is [y < c_{x+1}] - [y < c_x] under the mask; y < c <=> y < ceil(c) for an integer y).
+// Thread t owns the R = ceil(Tx / 256) consecutive rows t R .. t R + R - 1: its sum, an inclusive scan over the
+// wave's lanes (shuffles), the four wave totals through LDS, then the thread walks its rows again from its
+// exclusive prefix and leaves e_1 .. e_Tx in LDS ([Tx + 1] ints, 32 KiB at Tx = 8192).  fp32 terms add exactly
+// in float64 (24-bit terms, 2^13 of them at most: exact while their exponents span < 16 binades, and frame counts
+// do), so the boundaries do not depend on how the scan splits the rows.  col_row is mas_runs_kernel's search, the last row whose start <= y, over the LDS starts: a row of
+// length 0 shares its start with the next row, and the tie goes to the later, non-empty one.
+// lengths = (t_x, t_y) is what the forward crop windows on; run_lengths = (t_x, t_cov) ends the last row's run
+// for mas_expand_kernel and the backward consumers.  No atomics, fixed order.
+constexpr int kDurLdsHead = 32;  // bytes: the four wave totals (double) ahead of the starts; keeps them 16-byte aligned
+__global__ __launch_bounds__(256) void duration_path_kernel(const float *__restrict__ durations,
+                                                            const int64_t *__restrict__ x_lengths,
+                                                            const int64_t *__restrict__ y_lengths, int Tx, int Ty,
+                                                            int32_t *__restrict__ lengths,
+                                                            int32_t *__restrict__ run_lengths,
+                                                            int32_t *__restrict__ row_start, float *__restrict__ dur,
+                                                            int32_t *__restrict__ col_row) {
+    extern __shared__ __attribute__((aligned(16))) char dp_smem[];
+    double *wave_tot = reinterpret_cast<double *>(dp_smem);           // [4]
+    int32_t *e = reinterpret_cast<int32_t *>(dp_smem + kDurLdsHead);  // [Tx + 1]: e[x] = first frame of row x
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & (kWave - 1), wave = tid >> 6;
+    const int t_x = (int)min(max(x_lengths[b], (int64_t)0), (int64_t)Tx);
+    const int t_y = (int)min(max(y_lengths[b], (int64_t)0), (int64_t)Ty);
+    const float *d = durations + (size_t)b * Tx;
+    const int R = (Tx + 255) >> 8;
+    const int x0 = tid * R, x1 = min(x0 + R, t_x);  // this thread's rows that count: [x0, x1)
+
+    double s = 0.0;
+    for (int x = x0; x < x1; ++x) {
+        const float v = d[x];
+        s += v > 0.f ? (double)v : 0.0;  // false for NaN
+    }
+    double inc = s;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const double up = __shfl_up(inc, off);
+        if (lane >= off) inc += up;
+    }
+    if (lane == kWave - 1) wave_tot[wave] = inc;
+    __syncthreads();
+    double c = inc - s;  // the sum of the rows before x0
+    for (int w = 0; w < wave; ++w) c += wave_tot[w];
+    if (tid == 0) e[0] = 0;
+    const double cap = (double)t_y;
+    for (int x = x0; x < min(x0 + R, Tx); ++x) {
+        if (x < x1) {
+            const float v = d[x];
+            c += v > 0.f ? (double)v : 0.0;
+        }
+        e[x + 1] = (int)fmin(ceil(c), cap);  // rows >= t_x: e_{t_x}
+    }
+    __syncthreads();
+
+    const int t_cov = e[t_x];
+    if (tid == 0) {
+        if (lengths) {
+            lengths[2 * b] = t_x;
+            lengths[2 * b + 1] = t_y;
+        }
+        if (run_lengths) {
+            run_lengths[2 * b] = t_x;
+            run_lengths[2 * b + 1] = t_cov;
+        }
+    }
+    for (int x = tid; x < Tx; x += 256) {
+        const bool in = x < t_x;
+        if (row_start) row_start[(size_t)b * Tx + x] = in ? e[x] : -1;
+        if (dur) dur[(size_t)b * Tx + x] = in ? (float)(e[x + 1] - e[x]) : 0.f;
+    }
+    if (!col_row) return;
+    for (int yy = tid; yy < Ty; yy += 256) {
+        int row = -1;
+        if (yy < t_cov) {  // t_cov > 0: t_x >= 1 and e[0] = 0 <= yy
+            int lo = 0, hi = t_x - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (e[mid] <= yy) lo = mid; else hi = mid - 1;
+            }
+            row = lo;
+        }
+        col_row[(size_t)b * Ty + yy] = row;
+    }
+}
+
 // mu_y[b,c,y] = mu_x[b,c,col_row[b,y]] (0 where col_row < 0): attn^T mu_x on a one-hot attn is exactly
 // this gather (every other term is 0 * finite).  Backward: dmu_x[b,c,x] = sum over the run of row x
 // of dmu_y[b,c,y], in ascending y (deterministic; no atomics).
@@ -1627,6 +1717,30 @@ extern "C" int mtts_prior_maximum_path(const float *mu_x, const float *y, const 
         rc = mtts::check_launch("mas_runs_kernel");
     }
     return rc;
+}
+
+extern "C" int mtts_duration_path(const float *durations, const int64_t *x_lengths, const int64_t *y_lengths, int32_t B,
+                                  int32_t Tx, int32_t Ty, float *path, int32_t *lengths_out, int32_t *run_lengths_out,
+                                  int32_t *row_start_out, float *dur_out, int32_t *col_row_out, void *hip_stream) {
+    MTTS_CHECK_ARG(B >= 0 && Tx >= 1 && Ty >= 1, "duration_path: bad shape");
+    if (Tx > MTTS_MAS_MAX_TX)
+        return mtts::fail(MTTS_ERR_SHAPE, "duration_path: Tx > MTTS_MAS_MAX_TX (8192) is not supported");
+    if (B > 65535) return mtts::fail(MTTS_ERR_SHAPE, "duration_path: B > 65535");
+    MTTS_CHECK_ARG(durations && x_lengths && y_lengths, "duration_path: null input");
+    // the dense writer reads the runs back: the caller holds them (no workspace)
+    MTTS_CHECK_ARG(!path || (row_start_out && run_lengths_out), "duration_path: path needs row_start_out and run_lengths_out");
+    if (B == 0) return MTTS_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const size_t shmem = kDurLdsHead + ((size_t)Tx + 1) * 4;  // <= 32 KiB + 36 B
+    hipLaunchKernelGGL(duration_path_kernel, dim3(B), dim3(256), shmem, st, durations, x_lengths, y_lengths, Tx, Ty,
+                       lengths_out, run_lengths_out, row_start_out, dur_out, col_row_out);
+    int rc = mtts::check_launch("duration_path_kernel");
+    if (rc || !path) return rc;
+    dim3 grid((Ty + 1023) / 1024, Tx, B);
+    const int vec4 = (Ty % 4 == 0) && ((uintptr_t)path % 16 == 0);
+    hipLaunchKernelGGL((mas_expand_kernel<float, false>), grid, dim3(256), 0, st, row_start_out, run_lengths_out, path, Tx,
+                       Ty, vec4);
+    return mtts::check_launch("mas_expand_kernel");
 }
 
 extern "C" int mtts_expand_rows_fwd(const float *src, const int32_t *col_row, int32_t B, int32_t C, int32_t Tx,

@@ -36,6 +36,7 @@ _SIGNATURES: dict[str, tuple] = {
     "mtts_prior_maximum_path_workspace_size": (_SZ, [_I32, _I32, _I32]),
     "mtts_prior_maximum_path": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P,
                                                _SZ, _P]),
+    "mtts_duration_path": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "mtts_expand_rows_fwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "mtts_expand_rows_bwd": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "mtts_segment_crop_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P,

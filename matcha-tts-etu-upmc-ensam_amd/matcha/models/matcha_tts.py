@@ -121,6 +121,31 @@ class MatchaTTS(BaseLightningClass):
             mu_square = torch.sum(factor * (mu_x ** 2), 1).unsqueeze(-1)
             return y_square - y_mu_double + mu_square + const
 
+    def _encoder_ctx(self, device_type):
+        """The text encoder's precision policy (encoder_precision, see forward) as a context manager."""
+        enc_prec = self.encoder_precision or O.encoder_precision_default()
+        if enc_prec == "fp32":
+            return torch.autocast(device_type=device_type, enabled=False)
+        if enc_prec == "bf16x3":
+            return O.precise_forward("bf16x3")
+        if enc_prec == "fp32fwd":
+            return O.precise_forward("fp32")
+        if enc_prec == "bf16x6":
+            return O.precise_forward("bf16x6")
+        return _nullctx()
+
+    @torch.no_grad()
+    def align(self, x, x_lengths, y, y_lengths):
+        """The model's own alignment durations, int64 [B, Tx]: the frames MAS gives each text token (0 past
+        x_lengths) -- what one stores once and trains on later with use_precomputed_durations=True
+        (``forward(durations=...)``).  The encoder runs under forward's precision policy and the alignment is
+        forward's (prior_maximum_path, runs only), so in the same mode a forward on these durations sees the
+        alignment the MAS forward found.  CUDA tensors only."""
+        with self._encoder_ctx(x.device.type):
+            mu_x, _, _ = self.encoder(x, x_lengths)
+        _, dur, _, _, _ = monotonic_align.prior_maximum_path(mu_x, y, x_lengths, y_lengths, dense=False)
+        return dur.to(torch.int64)
+
     def forward(self, x, x_lengths, y, y_lengths, out_size=None, cond=None, durations=None, *, t=None, z=None,
                 segments=1, out_offset=None):
         """Returns (dur_loss, prior_loss, diff_loss, attn) -- matcha_tts.py:247-325.  ``t``/``z``
@@ -133,9 +158,14 @@ class MatchaTTS(BaseLightningClass):
         drawn on the device from torch's generator (a replayed graph draws fresh ones), ``out_offset``
         (keyword-only, int tensor [B], clamped on the device to [0, max(t_y - S, 0)]) injects them.  ``y_mask``
         has length S there; the reference's sequence_mask(y_cut_lengths) (:308) has length max(cut_len), which
-        is S whenever any utterance reaches S frames -- and the reference cannot run otherwise.  CPU tensors,
-        use_precomputed_durations and MTTS_SEGMENT_HOST=1 keep the reference's host-side crop (Python's
-        ``random``, a device->host copy, the dense attn matmul).  ``segments`` = n > 1 (keyword-only, the
+        is S whenever any utterance reaches S frames -- and the reference cannot run otherwise.  CPU tensors
+        and MTTS_SEGMENT_HOST=1 keep the reference's host-side crop (Python's ``random``, a device->host copy,
+        the dense attn matmul).  use_precomputed_durations=True (:273-274) takes ``durations`` ([B,Tx] or
+        [B,1,Tx], e.g. ``align``'s) instead of searching: on CUDA one launch turns them into the same run-length
+        alignment MAS returns (monotonic_align.duration_path), so mu_y is the gather and out_size the device
+        crop, with no MAS kernel and no host sync in the step; durations that cover fewer frames than y_lengths
+        leave the rest unaligned (attn and mu_y zero there), more are cut at y_lengths, as generate_path under
+        the mask.  ``segments`` = n > 1 (keyword-only, the
         Trainer's merged micro-batches): the batch is n equal micro-batches stacked along dim 0 and each loss
         is returned per micro-batch (a [n] tensor, every one normalised by its own micro-batch's lengths, as n
         separate forwards would) -- every other op of the model is per utterance."""
@@ -156,31 +186,33 @@ class MatchaTTS(BaseLightningClass):
             if t is None:
                 t = torch.rand([x.shape[0], 1, 1], device=x.device, dtype=torch.float32)
             self.decoder.estimator.prefetch(t, side)
-        enc_prec = self.encoder_precision or O.encoder_precision_default()
-        if enc_prec == "fp32":
-            enc_ctx = torch.autocast(device_type=x.device.type, enabled=False)
-        elif enc_prec == "bf16x3":
-            enc_ctx = O.precise_forward("bf16x3")
-        elif enc_prec == "fp32fwd":
-            enc_ctx = O.precise_forward("fp32")
-        elif enc_prec == "bf16x6":
-            enc_ctx = O.precise_forward("bf16x6")
-        else:
-            enc_ctx = _nullctx()
-        with enc_ctx:
+        with self._encoder_ctx(x.device.type):
             mu_x, logw, x_mask = self.encoder(x, x_lengths)
         y_max_length = y.shape[-1]
         y_mask = O.sequence_mask_f32(y_lengths, y_max_length).unsqueeze(1)  # sequence_mask(...).to(x_mask), one launch
         runs = None
+        # out_size on the device: the window is cut from the runs, the dense [B,Tx,Ty] path is never written
+        crop_dev = out_size is not None and x.is_cuda and os.environ.get("MTTS_SEGMENT_HOST", "0") != "1"
+        # what the forward crop windows on: (t_x, t_y); the runs carry what ends the last row's run (the same for MAS)
+        lens = None
         if self.use_precomputed_durations:
-            attn_mask = x_mask.unsqueeze(-1) * y_mask.unsqueeze(2)
-            attn = generate_path(durations.squeeze(1), attn_mask.squeeze(1))
-            dur = torch.sum(attn, -1)
+            if durations is None:
+                raise ValueError("use_precomputed_durations=True: forward needs `durations` ([B,Tx] or [B,1,Tx], "
+                                 "e.g. MatchaTTS.align's)")
+            if x.is_cuda and os.environ.get("MTTS_SEGMENT_HOST", "0") != "1":
+                # :273-274 on runs (monotonic_align.duration_path): one launch instead of generate_path's cumsum,
+                # [B*Tx,Ty] mask and elementwise passes; the consumers below are the MAS branch's
+                with torch.no_grad():
+                    attn, dur, col_row, row_start, lens, run_lens = monotonic_align.duration_path(
+                        durations, x_lengths, y_lengths, y_max_length, dense=not crop_dev)
+                runs = (col_row, row_start, run_lens)
+            else:
+                attn_mask = x_mask.unsqueeze(-1) * y_mask.unsqueeze(2)
+                attn = generate_path(durations.squeeze(1), attn_mask.squeeze(1))
+                dur = torch.sum(attn, -1)
         else:
             # :276-288 fused on the GPU: lattice (log_prior) * attn_mask -> maximum_path -> sum(attn, -1),
             # with the attention mask taken from the lengths (never materialised)
-            # out_size on the device: the window is cut from the runs, the dense [B,Tx,Ty] path is never written
-            crop_dev = out_size is not None and x.is_cuda and os.environ.get("MTTS_SEGMENT_HOST", "0") != "1"
             with torch.no_grad():
                 attn, dur, col_row, row_start, lens = monotonic_align.prior_maximum_path(mu_x, y, x_lengths,
                                                                                           y_lengths,
@@ -201,8 +233,9 @@ class MatchaTTS(BaseLightningClass):
             # :290-315 in one launch: y_cut, mu_y_cut = the window of attn^T @ mu_x, attn_cut and the mask
             # last_seg: int32 [B, 2] = (offset, cut_len) of this forward's windows (inside a captured step, the
             # tensor every replay rewrites)
-            y, mu_y, attn, y_mask, self.last_seg = monotonic_align.segment_crop(y, mu_x, *runs, out_size,
-                                                                               offsets=out_offset)
+            y, mu_y, attn, y_mask, self.last_seg = monotonic_align.segment_crop(y, mu_x, runs[0], runs[1], lens,
+                                                                               out_size, offsets=out_offset,
+                                                                               run_lengths=runs[2])
         elif out_size is not None:  # :290-312 (host-side random crop, as the reference)
             if out_offset is not None:
                 raise ValueError("out_offset injects the device crop's windows; the host-side crop draws its own")

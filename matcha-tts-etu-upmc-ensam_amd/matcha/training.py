@@ -38,6 +38,9 @@ Synthetic LJSpeech-shaped batches: token ids ~ U{1..149}, lengths ~ 
 with element 0 = max, mels ~ N(0, 1) zeroed past the length.  A batch dict may carry "t" [B, 1, 1] and
 "z" [B, n_feats, Ty]: the CFM randomness injected for parity tests (MatchaTTS.forward's keywords); with
 TrainConfig.out_size = S, "z" is [B, n_feats, S] and "out_offset" [B] injects the segment windows.
+"durations" ([B, Tx] or [B, 1, Tx], any real dtype; e.g. MatchaTTS.align's) goes to a
+MatchaTTS(use_precomputed_durations=True) as forward's ``durations``: the captured step then holds one
+duration_path launch in place of the MAS kernels, and a replay reads the batch's durations from its static buffer.
 """
 from __future__ import annotations
 
@@ -383,7 +386,8 @@ class Trainer:
                 else contextlib.nullcontext()
             with ctx, first:
                 # parity tests' CFM randomness and segment windows
-                inject = {k: batch[k] for k in ("t", "z", "out_offset") if k in batch}
+                # (and a use_precomputed_durations model's durations)
+                inject = {k: batch[k] for k in ("t", "z", "out_offset", "durations") if k in batch}
                 if self.cfg.out_size is not None:
                     inject["out_size"] = self.cfg.out_size
                 seg = batch.get("_segments", 1)
@@ -619,6 +623,8 @@ class Trainer:
                 raise ValueError(f"data parallel graph step: per-rank batch sizes differ ({-nbmin}..{bmax})")
             b = dict(b)
             if b["x"].shape[1] < tx:
+                if "durations" in b:  # [B,Tx] or [B,1,Tx]: along Tx, like x (rows past x_lengths count for nothing)
+                    b["durations"] = torch.nn.functional.pad(b["durations"], (0, tx - b["durations"].shape[-1]))
                 b["x"] = torch.nn.functional.pad(b["x"], (0, tx - b["x"].shape[1]))
             if b["y"].shape[2] < ty:
                 b["y"] = torch.nn.functional.pad(b["y"], (0, ty - b["y"].shape[2]))

@@ -11,6 +11,8 @@ fallback, __init__.py:8-37, uses the opposite tie rule and is NOT the parity tar
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from matcha import _native as N
@@ -146,6 +148,74 @@ def prior_maximum_path(mu_x: torch.Tensor, y: torch.Tensor, x_lengths: torch.Ten
     return out + (lattice,) if return_lattice else out
 
 
+def duration_runs_host(d, t_x: int, t_y: int):
+    """The device's duration rule restated in Python numbers (include/mtts.h, mtts_duration_path): for one
+    utterance's durations ``d`` (a sequence of Tx numbers), t_x <= Tx text rows and t_y frames, returns
+    (row_start [Tx], dur [Tx], col_row [t_y], t_cov).  Row x < t_x covers the frames [e_x, e_{x+1}) with
+    e_x = min(ceil(c_x), t_y) and c the float64 running sum of max(d, 0) (NaN counts as 0); -1 / 0 past t_x;
+    col_row is -1 from t_cov = e_{t_x} on.  It is generate_path(d, x_mask * y_mask) (utils/model.py) on runs."""
+    Tx = len(d)
+    t_x, t_y = min(max(int(t_x), 0), Tx), max(int(t_y), 0)
+    c, e = 0.0, [0]
+    for x in range(t_x):
+        v = float(d[x])
+        c += v if v > 0 else 0.0
+        e.append(int(math.ceil(min(c, float(t_y)))))  # = min(ceil(c), t_y): t_y is an integer
+    row_start = e[:t_x] + [-1] * (Tx - t_x)
+    dur = [e[x + 1] - e[x] for x in range(t_x)] + [0] * (Tx - t_x)
+    col_row = [-1] * t_y
+    for x in range(t_x):
+        col_row[e[x]:e[x + 1]] = [x] * (e[x + 1] - e[x])
+    return row_start, dur, col_row, e[t_x]
+
+
+def duration_path(durations: torch.Tensor, x_lengths: torch.Tensor, y_lengths: torch.Tensor, Ty: int, *,
+                  dense: bool = True):
+    """The alignment of precomputed durations (matcha_tts.py:273-274, use_precomputed_durations=True) as runs:
+    generate_path(durations, x_mask * y_mask) and its sum(-1) without the cumsum, the [B*Tx, Ty] mask and the
+    elementwise passes over [B,Tx,Ty] (csrc/mas.hip: duration_path_kernel -> mas_expand_kernel); the rule is
+    duration_runs_host's.
+
+    durations [B,Tx] or [B,1,Tx], any real or integer dtype (converted to fp32); x_lengths, y_lengths [B]; ``Ty``
+    the padded mel length.  Returns (attn [B,Tx,Ty] fp32, dur [B,Tx] fp32 = attn.sum(-1), col_row [B,Ty] int32,
+    row_start [B,Tx] int32, lengths [B,2] int32 = (t_x, t_y), run_lengths [B,2] int32 = (t_x, t_cov)): the
+    durations need not cover t_y frames, so the last row's run ends at t_cov.  expand_rows and the backward of
+    segment_crop take run_lengths; segment_crop's forward windows on lengths.  ``dense=False``: attn is None and
+    the [B,Tx,Ty] write is skipped.  No gradient, no host sync."""
+    N.require_device(durations, x_lengths, y_lengths)
+    if durations.dim() == 3 and durations.shape[1] == 1:
+        durations = durations[:, 0]
+    if durations.dim() != 2 or durations.is_complex() or durations.dtype == torch.bool:
+        raise ValueError(f"duration_path expects real durations [B,Tx] or [B,1,Tx], got {tuple(durations.shape)} "
+                         f"{durations.dtype}")
+    B, Tx = durations.shape
+    Ty = int(Ty)
+    if tuple(x_lengths.shape) != (B,) or tuple(y_lengths.shape) != (B,):
+        raise ValueError(f"duration_path: x_lengths / y_lengths must be [B] = [{B}], got {tuple(x_lengths.shape)}, "
+                         f"{tuple(y_lengths.shape)}")
+    if Tx < 1 or Ty < 1:
+        raise ValueError(f"duration_path: empty shape Tx={Tx}, Ty={Ty}")
+    _check_tx(Tx)
+    d = durations.detach().to(torch.float32).contiguous()
+    xl = x_lengths.detach().to(torch.int64).contiguous()
+    yl = y_lengths.detach().to(torch.int64).contiguous()
+    dev = d.device
+    attn = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev) if dense else None
+    dur = torch.empty((B, Tx), dtype=torch.float32, device=dev)
+    col_row = torch.empty((B, Ty), dtype=torch.int32, device=dev)
+    row_start = torch.empty((B, Tx), dtype=torch.int32, device=dev)
+    lengths = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    run_lengths = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    if B == 0:
+        return attn, dur, col_row, row_start, lengths, run_lengths
+    with torch.cuda.device(dev):
+        rc = N.lib().mtts_duration_path(N.ptr(d), N.ptr(xl), N.ptr(yl), B, Tx, Ty, N.ptr(attn), N.ptr(lengths),
+                                        N.ptr(run_lengths), N.ptr(row_start), N.ptr(dur), N.ptr(col_row),
+                                        N.stream_handle(dev))
+    N.check(rc, "mtts_duration_path")
+    return attn, dur, col_row, row_start, lengths, run_lengths
+
+
 class _ExpandRows(torch.autograd.Function):
     """mu_y = attn^T @ mu_x for a hard alignment (matcha_tts.py:314-315) as a gather of mu_x columns;
     backward sums each text row's run of frames (deterministic segment sums, no atomics)."""
@@ -195,7 +265,7 @@ class _SegmentCrop(torch.autograd.Function):
     on the zero-padded full-length gradient)."""
 
     @staticmethod
-    def forward(ctx, mu_x, y, col_row, row_start, lengths, out_size, offsets, words, want_attn):
+    def forward(ctx, mu_x, y, col_row, row_start, lengths, out_size, offsets, words, want_attn, run_lengths):
         ctx.in_dtype = mu_x.dtype
         mu_x = mu_x.to(torch.float32).contiguous()
         B, C, Tx = mu_x.shape
@@ -210,7 +280,8 @@ class _SegmentCrop(torch.autograd.Function):
                 N.ptr(y), N.ptr(mu_x), N.ptr(col_row), N.ptr(lengths), N.ptr(words), N.ptr(offsets), B, C, Tx, Ty, S,
                 N.ptr(y_cut), N.ptr(mu_y_cut), N.ptr(attn_cut), N.ptr(mask), N.ptr(seg), N.stream_handle(dev)),
                 "mtts_segment_crop_fwd")
-        ctx.save_for_backward(row_start, lengths, seg)
+        # the backward ends the last row's run at run_lengths' frame count (duration_path: t_cov <= t_y)
+        ctx.save_for_backward(row_start, run_lengths, seg)
         ctx.shape = (B, C, Tx, S)
         ctx.mark_non_differentiable(*(t for t in (y_cut, attn_cut, mask, seg) if t is not None))
         return y_cut, mu_y_cut, attn_cut, mask, seg
@@ -225,12 +296,13 @@ class _SegmentCrop(torch.autograd.Function):
             N.check(N.lib().mtts_segment_crop_bwd(N.ptr(d_mu_y), N.ptr(row_start), N.ptr(lengths), N.ptr(seg), B, C, Tx,
                                                   S, N.ptr(dx), N.stream_handle(d_mu_y.device)),
                     "mtts_segment_crop_bwd")
-        return (dx.to(ctx.in_dtype),) + (None,) * 8
+        return (dx.to(ctx.in_dtype),) + (None,) * 9
 
 
 def segment_crop(y: torch.Tensor, mu_x: torch.Tensor, col_row: torch.Tensor, row_start: torch.Tensor,
                  lengths: torch.Tensor, out_size: int, *, offsets: torch.Tensor | None = None,
-                 words: torch.Tensor | None = None, want_attn: bool = True):
+                 words: torch.Tensor | None = None, want_attn: bool = True,
+                 run_lengths: torch.Tensor | None = None):
     """The reference's random mel segment (matcha_tts.py:290-315, forward(out_size=...)) on the device, for the
     alignment prior_maximum_path returned: every utterance is cut to a window of ``out_size`` frames.
 
@@ -240,8 +312,9 @@ def segment_crop(y: torch.Tensor, mu_x: torch.Tensor, col_row: torch.Tensor, row
     ``offsets`` (int tensor [B]) injects the windows, clamped on the device to [0, max(t_y - S, 0)].  Otherwise
     one 31-bit word per utterance is drawn ON THE DEVICE from torch's generator (no host sync; a replayed HIP
     graph draws fresh windows) and mapped by segment_offset_host's rule; ``words`` (int32 [B], tests) gives
-    the words instead."""
-    N.require_device(y, mu_x, col_row, row_start, lengths, offsets, words)
+    the words instead.  ``run_lengths`` (int32 [B,2], duration_path's (t_x, t_cov); default: ``lengths``) is what
+    the backward ends the last row's run at; the forward's window is drawn on ``lengths``."""
+    N.require_device(y, mu_x, col_row, row_start, lengths, offsets, words, run_lengths)
     if mu_x.dim() != 3 or y.dim() != 3 or mu_x.shape[:2] != y.shape[:2]:
         raise ValueError(f"segment_crop expects y [B,C,Ty] and mu_x [B,C,Tx], got {tuple(y.shape)}, "
                          f"{tuple(mu_x.shape)}")
@@ -251,6 +324,10 @@ def segment_crop(y: torch.Tensor, mu_x: torch.Tensor, col_row: torch.Tensor, row
     if tuple(col_row.shape) != (B, Ty) or tuple(row_start.shape) != (B, mu_x.shape[2]) or \
             tuple(lengths.shape) != (B, 2):
         raise ValueError("segment_crop: col_row / row_start / lengths are not this batch's alignment")
+    if run_lengths is None:
+        run_lengths = lengths
+    elif tuple(run_lengths.shape) != (B, 2) or run_lengths.dtype != torch.int32:
+        raise ValueError(f"segment_crop: run_lengths must be int32 [B,2] = [{B},2]")
     y = y.detach().to(torch.float32).contiguous()
     if offsets is not None:
         if tuple(offsets.shape) != (B,):
@@ -264,4 +341,4 @@ def segment_crop(y: torch.Tensor, mu_x: torch.Tensor, col_row: torch.Tensor, row
     else:
         words = torch.randint(0, 2 ** 31 - 1, (B,), device=y.device, dtype=torch.int32)
     return _SegmentCrop.apply(mu_x, y, col_row.contiguous(), row_start.contiguous(), lengths.contiguous(),
-                              int(out_size), offsets, words, want_attn)
+                              int(out_size), offsets, words, want_attn, run_lengths.contiguous())
