@@ -1,4 +1,4 @@
-"""ctypes binding of libmtts_hip.so (C ABI: include/mtts.h, include/mtts_decoder.h).
+"""ctypes binding of libmtts_hip.so (C ABI: include/mtts.h, include/mtts_decoder.h, include/mtts_vocoder.h).
 
 The product path has no fallback: if the library is missing or was built without a symbol, every
 op raises.  ``lib()`` loads lazily so that importing the package on a machine without a GPU (CI,
@@ -53,6 +53,12 @@ _SIGNATURES: dict[str, tuple] = {
     # (args, precision, tile_cfg, splits, out[6]) -> schedule id, splits, workgroups, resident per CU, rounds, fill
     "mtts_conv_gemm_plan": (ctypes.c_int, [_P, _I32, _I32, _I32, ctypes.POINTER(_I32 * 6)]),
     "mtts_conv_gemm_glds_occupancy": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_I32 * 2)]),
+    # include/mtts_vocoder.h (HiFi-GAN generator inference; hifi_gan/models.py drives them)
+    "mtts_voc_conv": (ctypes.c_int, [_P, _P]),  # (mtts_voc_conv_args *, stream)
+    "mtts_voc_upsample": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P]),
+    "mtts_voc_pre_workspace_size": (_SZ, [_I32, _I32, _I32]),
+    "mtts_voc_pre": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P]),
+    "mtts_voc_post": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F, _P]),
 }
 
 _lib = None

@@ -90,9 +90,12 @@ class MatchaTTS(BaseLightningClass):
         self.update_data_statistics(data_statistics)
 
     @torch.inference_mode()
-    def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, length_scale=1.0, *, z=None):
+    def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, length_scale=1.0, *, z=None, vocoder=None):
         """matcha_tts.py:179-245 (reference fork).  ``z`` (keyword-only, [B, n_feats, y_max_length_])
-        injects the ODE's initial noise for parity tests."""
+        injects the ODE's initial noise for parity tests.  ``vocoder`` (keyword-only, a ``hifi_gan.Generator``):
+        the result gains "wav" [B, L] = vocoder(mel) clamped to [-1, 1] (generate_HifiGan.py:110-116) and
+        "wav_lengths" = mel_lengths * samples per frame; padded frames are vocoded unmasked, as the reference
+        does -- cut at wav_lengths."""
         t0 = dt.datetime.now()
         mu_x, logw, x_mask = self.encoder(x, x_lengths)
         w_ceil = torch.ceil(torch.exp(logw) * x_mask) * length_scale
@@ -105,9 +108,13 @@ class MatchaTTS(BaseLightningClass):
         mu_y = torch.matmul(attn.squeeze(1).transpose(1, 2), mu_x.transpose(1, 2)).transpose(1, 2)
         decoder_outputs = self.decoder(mu_y, y_mask, n_timesteps, temperature, z=z)[:, :, :y_max_length]
         rtf = (dt.datetime.now() - t0).total_seconds() * 22050 / (decoder_outputs.shape[-1] * 256)
-        return {"encoder_outputs": mu_y[:, :, :y_max_length], "decoder_outputs": decoder_outputs,
-                "attn": attn[:, :, :y_max_length], "mel": denormalize(decoder_outputs, self.mel_mean, self.mel_std),
-                "mel_lengths": y_lengths, "rtf": rtf}
+        out = {"encoder_outputs": mu_y[:, :, :y_max_length], "decoder_outputs": decoder_outputs,
+               "attn": attn[:, :, :y_max_length], "mel": denormalize(decoder_outputs, self.mel_mean, self.mel_std),
+               "mel_lengths": y_lengths, "rtf": rtf}
+        if vocoder is not None:
+            out["wav"] = vocoder(out["mel"]).squeeze(1).clamp(-1, 1)
+            out["wav_lengths"] = y_lengths * vocoder.hop
+        return out
 
     def log_prior(self, mu_x, y):
         """matcha_tts.py:277-282 in fp32: -1/2 sum y^2 + sum mu*y - 1/2 sum mu^2 - n/2 log(2 pi)."""
