@@ -1,6 +1,6 @@
 """HiFi-GAN generator inference on the HIP kernels of include/mtts_vocoder.h (mel -> waveform).
 
-    from hifi_gan import AttrDict, Generator, save_wav
+    from hifi_gan import AttrDict, Generator, GriffinLimVocoder, save_wav
 """
 from __future__ import annotations
 
@@ -9,10 +9,12 @@ import wave
 import numpy as np
 import torch
 
+from matcha.utils.audio_process import GriffinLimVocoder  # the checkpoint-free vocoder, same call shape
+
 from .env import AttrDict
 from .models import Generator
 
-__all__ = ["AttrDict", "Generator", "save_wav"]
+__all__ = ["AttrDict", "Generator", "GriffinLimVocoder", "save_wav"]
 
 
 def save_wav(path, wav, sampling_rate: int) -> None:

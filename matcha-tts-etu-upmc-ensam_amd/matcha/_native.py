@@ -1,4 +1,5 @@
-"""ctypes binding of libmtts_hip.so (C ABI: include/mtts.h, include/mtts_decoder.h, include/mtts_vocoder.h).
+"""ctypes binding of libmtts_hip.so (C ABI: include/mtts.h, include/mtts_decoder.h, include/mtts_vocoder.h,
+include/mtts_griffinlim.h).
 
 The product path has no fallback: if the library is missing or was built without a symbol, every
 op raises.  ``lib()`` loads lazily so that importing the package on a machine without a GPU (CI,
@@ -59,6 +60,10 @@ _SIGNATURES: dict[str, tuple] = {
     "mtts_voc_pre_workspace_size": (_SZ, [_I32, _I32, _I32]),
     "mtts_voc_pre": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P]),
     "mtts_voc_post": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F, _P]),
+    # include/mtts_griffinlim.h (inverse mel + Griffin-Lim; matcha/utils/audio_process.py drives them)
+    "mtts_gl_inverse_mel": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _P]),
+    "mtts_gl_synthesis": (ctypes.c_int, [_P, _P, _P, _F, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "mtts_gl_analysis": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
 }
 
 _lib = None

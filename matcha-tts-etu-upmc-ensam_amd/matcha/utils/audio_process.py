@@ -11,6 +11,9 @@ MAX_WAV_VALUE.  Differences: __call__ takes DEVICE tensors (batched; the referen
 on the CPU inside Dataset.__getitem__) and fails loudly without the HIP library -- there is no CPU
 path.  librosa (reference :4) is not a dependency: `slaney_mel_basis` computes the same basis
 (librosa.filters.mel, htk=False, norm="slaney") in float64 and stores it float32.
+
+The way back, mel -> waveform without a vocoder checkpoint (reference: generate.py:66-113, which uses torchaudio):
+InverseMelScale, GriffinLim and GriffinLimVocoder below, on the HIP kernels of include/mtts_griffinlim.h.
 """
 from __future__ import annotations
 
@@ -123,6 +126,273 @@ class MelSpectrogram:
                                           self.num_mels, 1e-5, N.ptr(out), N.stream_handle(y.device))
         N.check(rc, "mtts_mel_log_fwd")
         return out
+
+
+# ---- mel -> waveform without a vocoder checkpoint (reference: generate.py:66-113) ----------------------------------
+GL_NFFT, GL_HOP = 1024, 256  # include/mtts_griffinlim.h: the one STFT geometry the kernels serve
+
+_gl_tables: dict = {}
+
+
+def _gl_device_tables(device):
+    """(twiddle [1024, 2], window [1024]) on `device`: exp(-2 pi i k / 1024) computed in float64, stored fp32, and
+    the periodic Hann window."""
+    key = str(device)
+    if key not in _gl_tables:
+        a = torch.arange(GL_NFFT, dtype=torch.float64) * (-2.0 * math.pi / GL_NFFT)
+        tw = torch.stack([torch.cos(a), torch.sin(a)], 1).to(torch.float32)
+        _gl_tables[key] = (tw.to(device).contiguous(), torch.hann_window(GL_NFFT).to(device))
+    return _gl_tables[key]
+
+
+class InverseMelScale:
+    """torchaudio.transforms.InverseMelScale (same argument names and defaults) on one HIP kernel
+    (mtts_gl_inverse_mel): relu(pinv(M) @ mel), M this module's ``slaney_mel_basis``.  The pseudo-inverse is computed
+    once on the host in float64 and stored fp32; it is the minimum-norm least-squares solution torchaudio's
+    ``lstsq`` returns (M has full row rank).  Bins above f_max are written as exact zeros.
+
+    ``__call__(mel [B, n_mels, F], *, log_input=False) -> [B, n_stft, F]``.  The reference decides whether to
+    exponentiate a log-mel with a host-side ``if mel.min() < 0`` (generate.py:102); ``log_input=True`` applies the
+    exp inside the kernel instead, with no device-to-host synchronisation.  Device fp32 tensors only."""
+
+    def __init__(self, n_stft, n_mels=80, sample_rate=22050, f_min=0.0, f_max=None, norm="slaney", mel_scale="slaney"):
+        if norm != "slaney" or mel_scale != "slaney":
+            raise ValueError(f"InverseMelScale serves norm='slaney', mel_scale='slaney' only, got {norm!r}, "
+                             f"{mel_scale!r}")
+        if n_stft < 2 or not 1 <= n_mels <= 96:  # the kernel stages a tile's mel channels in LDS
+            raise ValueError(f"bad n_stft / n_mels (1 .. 96): {n_stft}, {n_mels}")
+        self.n_stft, self.n_mels, self.sample_rate = int(n_stft), int(n_mels), int(sample_rate)
+        self.f_min, self.f_max = float(f_min), float(sample_rate) / 2 if f_max is None else float(f_max)
+        basis = slaney_mel_basis(self.sample_rate, 2 * (self.n_stft - 1), self.n_mels, self.f_min, self.f_max)
+        pinv = torch.linalg.pinv(basis.double())  # [n_stft, n_mels]
+        reached = (basis != 0).any(0)
+        pinv[~reached] = 0.0  # a bin no filter reaches is zero in the minimum-norm solution (0 Hz, above f_max)
+        self.n_rows = int(reached.nonzero().max()) + 1 if reached.any() else 0  # rows from here on: never read
+        self.pinv = pinv.to(torch.float32).contiguous()
+        self._dev = {}
+
+    def to(self, *args, **kwargs):
+        """Accepted for torchaudio's call pattern; buffers follow the input's device on first use."""
+        return self
+
+    def _pinv_on(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self.pinv.to(device)
+        return self._dev[key]
+
+    def _launch(self, mel, out, *, log_input, inv_power=1.0, frame_major=False):
+        B, _, F = mel.shape
+        with torch.cuda.device(mel.device):
+            rc = N.lib().mtts_gl_inverse_mel(N.ptr(mel), N.ptr(self._pinv_on(mel.device)), N.ptr(out), B, self.n_mels,
+                                             self.n_stft, self.n_rows, F, int(bool(log_input)), float(inv_power),
+                                             int(frame_major), N.stream_handle(mel.device))
+        N.check(rc, "mtts_gl_inverse_mel")
+
+    def __call__(self, mel, *, log_input=False):
+        if mel.dim() != 3 or mel.shape[1] != self.n_mels:
+            raise ValueError(f"InverseMelScale expects mel [B, {self.n_mels}, F], got {tuple(mel.shape)}")
+        N.require_device(mel)
+        mel = mel.detach().to(torch.float32).contiguous()
+        out = torch.empty((mel.shape[0], self.n_stft, mel.shape[2]), dtype=torch.float32, device=mel.device)
+        self._launch(mel, out, log_input=log_input)
+        return out
+
+    forward = __call__
+
+
+class _GLState:
+    """The caller-owned buffers of one Griffin-Lim run on (B, F): spectra frame-major (include/mtts_griffinlim.h)."""
+
+    def __init__(self, B, F, device, n_mels=None):
+        with torch.inference_mode(False):  # graph-static buffers: later calls outside inference mode copy into them
+            e = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)  # noqa: E731
+            self.mel = e(B, n_mels, F) if n_mels else None
+            self.lin = e(B, F, GL_NFFT // 2 + 1)
+            self.ang0 = e(B, F, GL_NFFT // 2 + 1, 2)
+            self.spec = e(2, B, F, GL_NFFT // 2 + 1, 2)  # reb / tprev, ping-pong
+            self.frames = e(B, F, GL_NFFT)
+            self.wav = e(B, (F - 1) * GL_HOP)
+        self.graph = None
+
+
+class GriffinLim:
+    """torchaudio.transforms.GriffinLim (same argument names and defaults) on the HIP kernels of
+    include/mtts_griffinlim.h: ``__call__(spec [B, n_fft//2 + 1, F], *, angles=None) -> [B, (F - 1) * hop]``.
+
+    One run is a synthesis launch (phase update + inverse FFT + window) and an analysis launch (overlap-add gather +
+    window + FFT) per iteration, plus the first synthesis and the final gather; it is captured once per
+    (B, F, n_iter) into a HIP graph (at most 8 cached) and replayed; under an outer capture, or with ``graph =
+    False``, the same launches run eagerly.  With ``rand_init`` the initial phase has real and imaginary parts uniform
+    in [0, 1) -- not unit magnitude; torchaudio's behaviour -- drawn with torch's generator before the replay;
+    ``rand_init=False`` starts from the phase 1 + 0i in every bin, as torchaudio does, and is repeatable unseeded;
+    ``angles`` (complex [B, n_fft//2 + 1, F]) injects it instead.
+
+    Only n_fft = win_length = 1024 and hop_length = 256 are served (torchaudio's default hop_length = win_length // 2
+    is not: pass hop_length=256), ``length`` must be None and F >= 4 (fewer frames cannot be reflect-padded).
+    Device fp32 tensors only."""
+
+    _GRAPH_CACHE_MAX = 8
+    graph = True
+
+    def __init__(self, n_fft=1024, n_iter=32, win_length=None, hop_length=None, power=2.0, momentum=0.99, length=None,
+                 rand_init=True):
+        win_length = n_fft if win_length is None else win_length
+        hop_length = win_length // 2 if hop_length is None else hop_length
+        if (n_fft, win_length, hop_length) != (GL_NFFT, GL_NFFT, GL_HOP):
+            raise ValueError(f"GriffinLim serves n_fft = win_length = {GL_NFFT}, hop_length = {GL_HOP} only, got "
+                             f"n_fft={n_fft}, win_length={win_length}, hop_length={hop_length}")
+        if length is not None:
+            raise ValueError(f"GriffinLim serves length=None only, got {length}")
+        if not 0 <= momentum < 1:
+            raise ValueError(f"momentum must be in [0, 1), got {momentum}")
+        if n_iter < 0 or not power > 0:
+            raise ValueError(f"bad n_iter / power: {n_iter}, {power}")
+        self.n_fft, self.n_iter, self.win_length, self.hop_length = n_fft, int(n_iter), win_length, hop_length
+        self.power, self.momentum, self.length, self.rand_init = float(power), float(momentum), length, bool(rand_init)
+        self._graphs = {}
+
+    def to(self, *args, **kwargs):
+        return self
+
+    # ---- launches -------------------------------------------------------------------------------------------
+    def _launch(self, st, B, F, device, inverse_mel=None, n_iter=None):
+        """Every launch of one run on the current stream: (inverse mel,) synthesis, n_iter x (analysis, synthesis),
+        gather."""
+        lib, s = N.lib(), N.stream_handle(device)
+        tw, win = _gl_device_tables(device)
+        m = self.momentum / (1.0 + self.momentum)
+        n_iter = self.n_iter if n_iter is None else n_iter
+        with torch.cuda.device(device):
+            if inverse_mel is not None:
+                inverse_mel._launch(st.mel, st.lin, log_input=True, inv_power=1.0 / self.power, frame_major=True)
+
+            def synthesis(reb, tprev, normalize):
+                N.check(lib.mtts_gl_synthesis(N.ptr(st.lin), N.ptr(reb), N.ptr(tprev), m, normalize, N.ptr(tw),
+                                              N.ptr(win), N.ptr(st.frames), B, F, GL_NFFT, GL_HOP, s),
+                        "mtts_gl_synthesis")
+
+            synthesis(st.ang0, None, 0)
+            for i in range(n_iter):
+                N.check(lib.mtts_gl_analysis(N.ptr(st.frames), N.ptr(tw), N.ptr(win), N.ptr(st.spec[i % 2]), None, B, F,
+                                             GL_NFFT, GL_HOP, s), "mtts_gl_analysis")
+                synthesis(st.spec[i % 2], st.spec[(i + 1) % 2] if i else None, 1)
+            N.check(lib.mtts_gl_analysis(N.ptr(st.frames), None, N.ptr(win), None, N.ptr(st.wav), B, F, GL_NFFT,
+                                         GL_HOP, s), "mtts_gl_analysis")
+
+    def _fill(self, st, spec, mel, angles):
+        if mel is not None:
+            st.mel.copy_(mel)
+        else:
+            st.lin.copy_((spec if self.power == 1.0 else spec.pow(1.0 / self.power)).transpose(1, 2))
+        if angles is not None:
+            st.ang0.copy_(torch.view_as_real(angles.transpose(1, 2).to(torch.complex64).resolve_conj()))
+        elif self.rand_init:
+            st.ang0.uniform_(0.0, 1.0)
+        else:  # torchaudio: angles = torch.full(specgram.size(), 1) -- the phase 1 + 0i, deterministic
+            st.ang0[..., 0].fill_(1.0)
+            st.ang0[..., 1].zero_()
+
+    def _run(self, B, F, device, *, spec=None, mel=None, inverse_mel=None, angles=None):
+        if self.graph and not torch.cuda.is_current_stream_capturing():
+            key = (B, F, self.n_iter, str(device), inverse_mel is not None)
+            st = self._graphs.get(key)
+            if st is None:
+                if len(self._graphs) >= self._GRAPH_CACHE_MAX:
+                    self._graphs.pop(next(iter(self._graphs)))
+                st = _GLState(B, F, device, inverse_mel.n_mels if inverse_mel is not None else None)
+                cur = torch.cuda.current_stream(device)
+                side = torch.cuda.Stream(device)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):  # warm-up on the zeroed buffers: lazy code-object loads
+                    self._launch(st, B, F, device, inverse_mel, n_iter=min(self.n_iter, 2))
+                cur.wait_stream(side)
+                st.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(st.graph):
+                    self._launch(st, B, F, device, inverse_mel)
+                self._graphs[key] = st
+            self._fill(st, spec, mel, angles)
+            st.graph.replay()
+            return st.wav.clone()
+        st = _GLState(B, F, device, inverse_mel.n_mels if inverse_mel is not None else None)
+        self._fill(st, spec, mel, angles)
+        self._launch(st, B, F, device, inverse_mel)
+        return st.wav
+
+    def _check(self, x, rows, what, angles):
+        if x.dim() != 3 or x.shape[1] != rows:
+            raise ValueError(f"{what} must be [B, {rows}, F], got {tuple(x.shape)}")
+        if x.shape[2] < 4:
+            raise ValueError(f"Griffin-Lim needs at least 4 frames (fewer cannot be reflect-padded by "
+                             f"{GL_NFFT // 2} samples), got {x.shape[2]}")
+        if angles is not None and (not angles.is_complex() or
+                                   tuple(angles.shape) != (x.shape[0], GL_NFFT // 2 + 1, x.shape[2])):
+            raise ValueError(f"angles must be complex [B, {GL_NFFT // 2 + 1}, F], got {tuple(angles.shape)}")
+        N.require_device(x, angles)
+
+    def __call__(self, spec, *, angles=None):
+        self._check(spec, GL_NFFT // 2 + 1, "spec", angles)
+        with torch.no_grad():
+            spec = spec.detach().to(torch.float32)
+            B, _, F = spec.shape
+            if B == 0:
+                return torch.zeros(0, (F - 1) * GL_HOP, dtype=torch.float32, device=spec.device)
+            return self._run(B, F, spec.device, spec=spec, angles=angles)
+
+    forward = __call__
+
+    def rebuilt(self, spec, *, angles):
+        """Test hook: the first iteration's ``stft(istft(spec ** (1/power) * angles))`` as complex
+        [B, n_fft//2 + 1, F] (one synthesis and one analysis launch, eager)."""
+        self._check(spec, GL_NFFT // 2 + 1, "spec", angles)
+        B, _, F = spec.shape
+        dev = spec.device
+        with torch.no_grad():
+            st = _GLState(B, F, dev)
+            self._fill(st, spec.detach().to(torch.float32), None, angles)
+            tw, win = _gl_device_tables(dev)
+            with torch.cuda.device(dev):
+                s = N.stream_handle(dev)
+                N.check(N.lib().mtts_gl_synthesis(N.ptr(st.lin), N.ptr(st.ang0), None, 0.0, 0, N.ptr(tw), N.ptr(win),
+                                                  N.ptr(st.frames), B, F, GL_NFFT, GL_HOP, s), "mtts_gl_synthesis")
+                N.check(N.lib().mtts_gl_analysis(N.ptr(st.frames), N.ptr(tw), N.ptr(win), N.ptr(st.spec[0]), None, B,
+                                                 F, GL_NFFT, GL_HOP, s), "mtts_gl_analysis")
+            return torch.view_as_complex(st.spec[0]).transpose(1, 2).contiguous()
+
+
+class GriffinLimVocoder:
+    """The reference's checkpoint-free mel -> waveform path (generate.py:73-109: exp, InverseMelScale, 32 iterations
+    of GriffinLim with power 1), shaped like ``hifi_gan.Generator``: ``__call__(log_mel [B, num_mels, T]) ->
+    [B, 1, T * hop]`` with ``.hop`` samples per frame, so ``MatchaTTS.synthesise(..., vocoder=GriffinLimVocoder())``
+    works unchanged.  Griffin-Lim yields (T - 1) * hop samples; the last hop is zero padding.  Padded frames are
+    vocoded unmasked, like the HiFi-GAN path: cut at ``wav_lengths``.  The inverse mel runs inside the captured
+    graph: 2 * n_iter + 3 launches per call."""
+
+    def __init__(self, n_fft=1024, hop_size=256, num_mels=80, sampling_rate=22050, fmin=0, fmax=8000, n_iter=32):
+        self.griffin_lim = GriffinLim(n_fft=n_fft, n_iter=n_iter, win_length=n_fft, hop_length=hop_size, power=1.0)
+        self.inverse_mel = InverseMelScale(n_fft // 2 + 1, num_mels, sampling_rate, float(fmin),
+                                           None if fmax is None else float(fmax))
+        self.hop = hop_size
+        self.num_mels = num_mels
+
+    def to(self, *args, **kwargs):
+        return self
+
+    def eval(self):
+        return self
+
+    def __call__(self, log_mel, *, angles=None):
+        self.griffin_lim._check(log_mel, self.num_mels, "log_mel", angles)
+        with torch.no_grad():
+            mel = log_mel.detach().to(torch.float32)
+            B, _, T = mel.shape
+            out = torch.zeros(B, 1, T * self.hop, dtype=torch.float32, device=mel.device)
+            if B:
+                wav = self.griffin_lim._run(B, T, mel.device, mel=mel, inverse_mel=self.inverse_mel, angles=angles)
+                out[:, 0, :(T - 1) * self.hop] = wav
+            return out
+
+    forward = __call__
 
 
 def load_and_process_audio(file_path, mel_processor, device="cuda"):
