@@ -371,24 +371,37 @@ def spec_convT_dgrad(w):
                     True)
 
 
-def _run_pack(specs, prec, stream=None):
+def _pack_alloc(specs, prec):
+    """What _run_pack(specs, prec) needs from the current stream: (the output planes, the fp32 contiguous
+    sources of every job -- a conversion kernel, where a weight needs one, runs here too)."""
+    dev = specs[0].jobs[0][0].device
+    planes = 3 if prec == PACK_BF16_SPLIT3 else 2 if prec == PACK_BF16_SPLIT else 1
+    dt = torch.bfloat16 if prec in (PREC_BF16, PACK_BF16_SPLIT, PACK_BF16_SPLIT3) else torch.float32
+    outs = [torch.empty(planes * sp.rows, sp.Kp, device=dev, dtype=dt) for sp in specs]
+    return outs, [[_f32c(job[0]) for job in sp.jobs] for sp in specs]
+
+
+def _run_pack(specs, prec, stream=None, alloc=None):
     """prec: PREC_FP32, PREC_BF16, PACK_BF16_SPLIT ([2 * rows, Kp]: the hi plane, then the lo plane) or
     PACK_BF16_SPLIT3 ([3 * rows, Kp]: hi, mid, lo).
-    stream: launch there instead of the current stream (outputs are allocated on the current one)."""
+    stream: launch there instead of the current stream; the outputs and sources come from the current one, and
+    from the caller (alloc = _pack_alloc(specs, prec)) BEFORE `stream` was forked from it: the fork then orders
+    the launch after whatever the current stream did with that memory.  The caller keeps `alloc` alive until
+    `stream` is joined."""
     dev = specs[0].jobs[0][0].device
     split3 = prec == PACK_BF16_SPLIT3
     split = prec == PACK_BF16_SPLIT or split3
-    dt = torch.bfloat16 if prec in (PREC_BF16, PACK_BF16_SPLIT, PACK_BF16_SPLIT3) else torch.float32
-    outs = [torch.empty((3 if split3 else 2 if split else 1) * sp.rows, sp.Kp, device=dev, dtype=dt) for sp in specs]
+    if alloc is None:
+        if stream is not None:
+            raise ValueError("_run_pack on another stream: take _pack_alloc before forking it")
+        alloc = _pack_alloc(specs, prec)
+    outs, srcs = alloc
     njobs = sum(len(sp.jobs) for sp in specs)
     arr = (PackJob * njobs)()
     i = 0
-    keep = []
-    for sp, out in zip(specs, outs):
+    for sp, out, sp_srcs in zip(specs, outs, srcs):
         es = out.element_size()
-        for (w, r0, rows, c0, kpj, C, nt, sr, sc, sj, j0, js) in sp.jobs:
-            src = _f32c(w)
-            keep.append(src)
+        for (w, r0, rows, c0, kpj, C, nt, sr, sc, sj, j0, js), src in zip(sp.jobs, sp_srcs):
             j = arr[i]
             j.src, j.dst = src.data_ptr(), out.data_ptr() + (r0 * sp.Kp + c0) * es
             j.rows, j.C, j.ntaps, j.Kp, j.ld = rows, C, nt, kpj, sp.Kp
@@ -438,7 +451,7 @@ def weight_pack_scope(owner: torch.nn.Module):
         cache = pre[1]  # packed ahead on the side stream (prefetch_packs): wait for it
         torch.cuda.current_stream(pre[2].device).wait_stream(pre[2])
     else:
-        cache = _pack_plan_now(plan, prec)
+        cache, _ = _pack_plan_now(plan, prec)
     tok = _PACK_SCOPE.set((plan, cache, prec))
     nseed = owner.__dict__.get("_mtts_seed_count", 0)
     dev = next(owner.parameters()).device
@@ -454,32 +467,44 @@ def weight_pack_scope(owner: torch.nn.Module):
         owner.__dict__["_mtts_seed_count"] = seeds["used"]
 
 
-def _pack_plan_now(plan, prec, stream=None):
+def _pack_plan_now(plan, prec, fork=None):
     """Every layout in `plan` for this precision (the backward's transposed ones too when grad is
-    enabled), a few launches per kind -> {key: packed}."""
+    enabled), a few launches per kind -> ({key: packed}, the stream launched on or None for the current one).
+    fork: a callable returning the stream to launch on, called ONCE, after every output and source is taken
+    from the current stream (not at all when there is nothing to pack)."""
     grad = torch.is_grad_enabled()
     kinds = (prec, PACK_BF16_SPLIT, PACK_BF16_SPLIT3, PREC_FP32) if prec == PREC_BF16 else (prec,)
-    cache = {}
+    groups = []
     for kind in kinds:
         specs = [sp for key, sp in plan.items()
                  if key[0] == kind and (grad or not sp.dgrad) and _pack_kind(sp, prec) == kind]
         if specs:
-            for sp, t in zip(specs, _run_pack(specs, kind, stream)):
-                cache[(kind,) + sp.key] = t
-    return cache
+            groups.append((kind, specs, _pack_alloc(specs, kind)))
+    stream = fork() if (fork is not None and groups) else None
+    cache = {}
+    for kind, specs, alloc in groups:
+        for sp, t in zip(specs, _run_pack(specs, kind, stream, alloc)):
+            cache[(kind,) + sp.key] = t
+    if stream is not None:  # sources (converted copies included) and outputs stay alive until the join
+        keep_for_side(*(t for _, _, (outs, srcs) in groups for t in outs + [x for sp in srcs for x in sp]))
+    return cache, stream
 
 
-def prefetch_packs(owner: torch.nn.Module, side) -> None:
-    """Packs `owner`'s known layouts NOW on `side` (outputs allocated on the current stream), for its next
-    weight_pack_scope -- which waits for `side` and skips its own packing.  The weights must not change
-    in between (one forward)."""
+def prefetch_packs(owner: torch.nn.Module, fork):
+    """Packs `owner`'s known layouts NOW on the side stream `fork()` returns, for its next weight_pack_scope --
+    which waits for that stream and skips its own packing.  The outputs are allocated on the current stream
+    first and `fork()` (which orders the side stream after the current one) is called once, after that: every
+    byte of a buffer is then written in an order that holds on both streams.  Returns the stream, or None when
+    there was nothing to pack (fork not called).  The weights must not change in between (one forward)."""
     plan = owner.__dict__.get("_mtts_pack_plan")
     if not plan:
-        return
+        return None
     prec = gemm_precision()
-    cache = _pack_plan_now(plan, prec, side)
-    keep_for_side(*cache.values())  # alive until the side stream is joined, used or not
+    cache, side = _pack_plan_now(plan, prec, fork)
+    if side is None:
+        return None
     owner.__dict__["_mtts_pack_pre"] = ((prec, torch.is_grad_enabled()), cache, side)
+    return side
 
 
 def packed(spec: PackSpec, prec: int) -> tuple[torch.Tensor, int]:
@@ -1869,20 +1894,26 @@ def _time_mlp_launch(e, w1, b1, w2, b2, ws, bs, outs):
 
 def time_mlp(e, linear_1, linear_2, proj_linears, pre=None):
     """(temb, [tp_i]) = (time_mlp(e), [lin_i(mish(temb))]) for nn.Linear modules; see _TimeMLP.  pre: the
-    forward's tensors from time_mlp_ahead (already joined)."""
+    forward's tensors from time_mlp_ahead_launch (already joined)."""
     ws = [lin.weight for lin in proj_linears]
     bs = [lin.bias for lin in proj_linears]
     out = _TimeMLP.apply(e, linear_1.weight, linear_1.bias, linear_2.weight, linear_2.bias, len(ws), pre, *ws, *bs)
     return out[0], list(out[1:])
 
 
-def time_mlp_ahead(e, linear_1, linear_2, proj_linears, side):
-    """The time MLP's forward launched on `side` now (outputs allocated on the current stream) -> the
-    `pre` tensors for time_mlp once the caller has joined `side`."""
+def time_mlp_ahead_alloc(e, linear_1, linear_2, proj_linears):
+    """The operands and outputs (allocated on the current stream) of the time MLP's forward, for
+    time_mlp_ahead_launch -- taken BEFORE the side stream is forked, see prefetch_packs."""
     w1, b1, w2, b2 = (_f32c(v) for v in (linear_1.weight, linear_1.bias, linear_2.weight, linear_2.bias))
     ws = [_f32c(lin.weight) for lin in proj_linears]
     bs = [_f32c(lin.bias) for lin in proj_linears]
-    outs = _time_mlp_alloc(e, w1, b1, w2, b2, ws, bs)
+    return e, w1, b1, w2, b2, ws, bs, _time_mlp_alloc(e, w1, b1, w2, b2, ws, bs)
+
+
+def time_mlp_ahead_launch(args, side):
+    """The time MLP's forward launched on `side` now -> the `pre` tensors for time_mlp once the caller has
+    joined `side`."""
+    e, w1, b1, w2, b2, ws, bs, outs = args
     keep_for_side(e, w1, b1, w2, b2, *ws, *bs, *outs[:4], *outs[4])  # alive until the side stream is joined
     with torch.cuda.stream(side):
         _time_mlp_launch(e, w1, b1, w2, b2, ws, bs, outs)

@@ -233,21 +233,27 @@ class Decoder(nn.Module):
         return ([r for r, *_ in self.Downsampling_Blocks] + [r for r, _ in self.Mid_Blocks]
                 + [r for r, *_ in self.Upsampling_Blocks])
 
-    def prefetch(self, t, side):
-        """Launches, on `side` (already ordered after the current stream), what this decoder's next forward
-        for CFM time t needs and nothing else produces: its weight packs and the time path (embedding +
-        time MLP forward).  Outputs are allocated on the current stream; forward waits for `side` where it
-        uses them (weight_pack_scope, _time_path) -- a Trainer step runs them beside the text encoder."""
-        O.prefetch_packs(self, side)
+    def prefetch(self, t, fork):
+        """Launches, on the side stream `fork()` returns (ordered after the current stream), what this decoder's
+        next forward for CFM time t needs and nothing else produces: its weight packs and the time path
+        (embedding + time MLP forward).  Every output is allocated on the current stream BEFORE the fork, so the
+        fork orders the side stream's writes after whatever the current stream did with that memory; forward
+        waits for the side stream where it uses them (weight_pack_scope, _time_path) -- a Trainer step runs them
+        beside the text encoder."""
         resnets = self._resnets()
         with torch.autocast("cuda", enabled=False):
             tt = t.detach().float().reshape(-1).contiguous()
             e = torch.empty((tt.numel(), self.time_embeddings.dim), dtype=torch.float32, device=tt.device)
+            tm = O.time_mlp_ahead_alloc(e, self.time_mlp.linear_1, self.time_mlp.linear_2, [r.mlp[1] for r in resnets])
+        side = O.prefetch_packs(self, fork)  # takes its planes and sources, then forks (once), then launches
+        if side is None:  # nothing to pack yet (the first forward): the fork is taken here
+            side = fork()
+        with torch.autocast("cuda", enabled=False):
             D.keep_for_side(tt, e)
             with torch.cuda.device(tt.device):
                 N.check(N.lib().mtts_time_embedding(N.ptr(tt), tt.numel(), self.time_embeddings.dim, 1000.0, N.ptr(e),
                                                     side.cuda_stream), "mtts_time_embedding")
-            pre = O.time_mlp_ahead(e, self.time_mlp.linear_1, self.time_mlp.linear_2, [r.mlp[1] for r in resnets], side)
+            pre = O.time_mlp_ahead_launch(tm, side)
         self.__dict__["_mtts_time_pre"] = (tt.data_ptr(), tt.numel(), e, pre, side)
 
     def _time_path(self, t):

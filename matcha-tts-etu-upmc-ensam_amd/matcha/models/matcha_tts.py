@@ -186,13 +186,11 @@ class MatchaTTS(BaseLightningClass):
         # instead of in compute_loss; the same distribution)
         # t is drawn BEFORE the fork: the side stream's time embedding reads it, and the fork orders the side
         # stream after the main stream's work up to that point only (drawn after it, the read raced the draw)
-        if x.is_cuda and _PREFETCH and t is None and D.side_fork_available():
-            t = torch.rand([x.shape[0], 1, 1], device=x.device, dtype=torch.float32)
-        side = D.side_fork() if (x.is_cuda and _PREFETCH) else None
-        if side is not None:
+        # and the fork is taken inside prefetch, AFTER its outputs are allocated on the main stream
+        if x.is_cuda and _PREFETCH and D.side_fork_available():
             if t is None:
                 t = torch.rand([x.shape[0], 1, 1], device=x.device, dtype=torch.float32)
-            self.decoder.estimator.prefetch(t, side)
+            self.decoder.estimator.prefetch(t, D.side_fork)
         with self._encoder_ctx(x.device.type):
             mu_x, logw, x_mask = self.encoder(x, x_lengths)
         y_max_length = y.shape[-1]
