@@ -1448,8 +1448,7 @@ int mtts_rope_qk(const float *x, float *y, int32_t rows, int32_t T, int32_t C, i
     if (n == 0) return MTTS_OK;
     const int D = C / H;
     const bool al = ((uintptr_t)x | (uintptr_t)y | (uintptr_t)cos_t | (uintptr_t)sin_t) % 16 == 0;
-    static const bool scalar_only = [] { const char *e = getenv("MTTS_ROPE_SCALAR"); return e && e[0] == '1'; }();
-    if (!scalar_only && al && C % 4 == 0 && D % 4 == 0 && rope_dims % 8 == 0 && n / 4 < INT32_MAX) {
+    if (al && C % 4 == 0 && D % 4 == 0 && rope_dims % 8 == 0 && n / 4 < INT32_MAX) {
         const int64_t n4 = n / 4;
         hipLaunchKernelGGL(rope_qk_vec4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
                            static_cast<hipStream_t>(hip_stream), reinterpret_cast<const float4 *>(x),

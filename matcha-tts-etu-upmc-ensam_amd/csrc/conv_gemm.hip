@@ -56,12 +56,6 @@ __device__ __forceinline__ bf16x8 tr_read8(const uint16_t *p, int row_stride) {
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-// -DMTTS_PIN_PREFETCH=0 builds the register-staged loops without the scheduling fence (A/B builds)
-#ifndef MTTS_PIN_PREFETCH
-#define MTTS_PIN_PREFETCH 1
-#endif
-constexpr bool g_pin_prefetch = MTTS_PIN_PREFETCH != 0;
-
 // -DMTTS_GEMM_TIMELINE=1 (diagnostic builds only, tools/r5/gemm_timeline.py): lane 0 of every wave of the
 // register-staged one-step schedule stamps the 100 MHz wall clock at each phase of each K step into g_tl
 // ([wave][kTlSlots]: HW ids, start, prologue, then per step: loads issued / MFMAs issued / LDS stored /
@@ -386,7 +380,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_kernel(mtts_conv_gemm_
 
     // The scheduling fence after each prefetch keeps its global loads ahead of the step's MFMAs: without it
     // the machine scheduler sank them behind all but the last few MFMAs (ISA of the fp32 64 x 64 schedule,
-    // round 5), so the vmcnt wait before store_tile exposed the whole global round trip every step.
+    // round 5), so the vmcnt wait before store_tile exposed the whole global round trip every step
+    // (profiles/r05/ab/pin_prefetch.txt; A/B last runnable at 3dd8270).
     if constexpr (DEPTH == 2) {
         // two K steps in flight: the loads of step kt+2 are issued before computing step kt, stored to
         // LDS after computing step kt+1 -- two compute phases cover each global round trip
@@ -396,13 +391,13 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_kernel(mtts_conv_gemm_
         mtts::lds_barrier();
         for (int kt = 0; kt < nk; kt += 2) {
             load_tile(R0, kbase + (kt + 2) * KB);
-            if (g_pin_prefetch) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             compute(0);
             store_tile(R1, 1);
             mtts::lds_barrier();
             if (kt + 1 >= nk) break;
             load_tile(R1, kbase + (kt + 3) * KB);
-            if (g_pin_prefetch) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             compute(1);
             store_tile(R0, 0);
             mtts::lds_barrier();
@@ -422,7 +417,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_kernel(mtts_conv_gemm_
         MTTS_TL(2);
         for (int kt = 0; kt < nk; ++kt) {
             load_tile(R0, kbase + (kt + 1) * KB);
-            if (g_pin_prefetch) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #if MTTS_GEMM_TIMELINE
             if (kt < kTlSteps) MTTS_TL(3 + 4 * kt);
 #endif
@@ -713,7 +708,8 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
                 // the dY row validity is a SELECT, not a multiply by a 0/1 mask: built with packed-fp32
                 // VALU ops, hipcc turned that multiply into v_pk_mul_f32 over the mask pair of two rows
                 // (op_sel:[0,1] op_sel_hi:[1,0]), which returned wrong, nondeterministic products under
-                // CU co-residency (tools/gpu_r2d.sh reproduces it, variant F fixes it)
+                // CU co-residency (tools/gpu_r2d.sh, last runnable at 3dd8270, reproduced it,
+                // variant F fixes it)
                 const bool yk = R.yok[c][h];
                 const float xm = R.xok[c][h] ? (p.a_scale ? R.xs[c][h] : 1.f) : 0.f;
                 float4 yf;
@@ -818,13 +814,13 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
             mtts::lds_barrier();
             for (int rb = r_begin; rb < r_end; rb += 2 * KB) {
                 load(R0, rb + 2 * KB);
-                if (g_pin_prefetch) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 compute(0);
                 store(R1, 1);
                 mtts::lds_barrier();
                 if (rb + KB >= r_end) break;
                 load(R1, rb + 3 * KB);
-                if (g_pin_prefetch) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 compute(1);
                 store(R0, 0);
                 mtts::lds_barrier();
@@ -836,7 +832,7 @@ __device__ __forceinline__ void wgrad_block(const WgradBatch &wb, const int vb) 
                 store(R0, buf);  // buf was last read two steps ago, before the previous barrier
                 mtts::lds_barrier();
                 load(R0, rb + KB);  // unconditional: past r_end every row is masked off (branch-free body)
-                if (g_pin_prefetch) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 compute(buf);
                 buf ^= 1;
             }

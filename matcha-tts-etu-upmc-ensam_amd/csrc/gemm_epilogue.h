@@ -187,12 +187,8 @@ enum : int {
     EK_DGELU = 4,    // fast GELU' on a bf16 aux, bf16 C; bias / dropout at run time; no C_pre / residual / c_scale
     EK_RELU32 = 5,   // ReLU, fp32 C; bias / dropout / residual / c_scale at run time; no C_pre (the text encoder's FFN)
     EK_DRELU32 = 6,  // ReLU' on an fp32 aux, fp32 C; the same run-time terms; no C_pre (its backward)
-};
+};  // (the ReLU kinds against the run-time epilogue: profiles/r05/ab/ek_relu.txt; A/B last runnable at 3dd8270)
 
-// -DMTTS_EK_RELU=0: the ReLU / ReLU' launches keep the run-time epilogue (A/B builds)
-#ifndef MTTS_EK_RELU
-#define MTTS_EK_RELU 1
-#endif
 __host__ __device__ inline int gemm_epilogue_kind(const mtts_conv_gemm_args &p) {
     const bool fast = p.flags & MTTS_GEMM_F_FAST_ACT, pre16 = p.flags & MTTS_GEMM_F_PRE_BF16,
                c16 = p.flags & MTTS_GEMM_F_C_BF16;
@@ -200,10 +196,8 @@ __host__ __device__ inline int gemm_epilogue_kind(const mtts_conv_gemm_args &p) 
     if (p.act == MTTS_ACT_GELU && fast && pre16 && c16 && p.C_pre && !p.residual && !p.c_scale) return EK_GELU;
     if (p.act == MTTS_ACT_DGELU && fast && pre16 && c16 && !p.C_pre && p.aux && !p.residual && !p.c_scale)
         return EK_DGELU;
-#if MTTS_EK_RELU
     if (p.act == MTTS_ACT_RELU && !p.C_pre && !c16) return EK_RELU32;
     if (p.act == MTTS_ACT_DRELU && !p.C_pre && !c16 && !pre16 && p.aux) return EK_DRELU32;
-#endif
     return EK_RT;
 }
 

@@ -56,14 +56,13 @@ GEMM_F_FAST_ACT = 0x8  # MTTS_GEMM_F_FAST_ACT: 1.5e-7-accurate erf in GELU epilo
 GEMM_F_PRE_BF16 = 0x10  # MTTS_GEMM_F_PRE_BF16: C_pre written / aux read as bf16
 WGRAD_F_DY_BF16 = 0x20  # MTTS_WGRAD_F_DY_BF16: the weight gradient's dY holds bf16
 GEMM_F_W_SPLIT = 0x40  # MTTS_GEMM_F_W_SPLIT: W holds a hi and a lo bf16 plane (two MFMAs per product)
-_FAST_ACT = os.environ.get("MTTS_EXACT_GELU") != "1"
 # Weight planes of the bf16-mixed forward GEMMs.  Split (two bf16 planes, hi + rounding residual): the
 # rounding of the fp32 weights is a static model perturbation and is the bf16 loss error
-# (tools/r3/precision_budget.py: prior 2.9e-4 / diff 2.1e-4 from weight rounding alone, activations
-# 3.8e-5 / 2.1e-5 at B=32) -- with split planes bf16-mixed meets the 1e-4 loss bar at the bench batch, at
-# ~+50 % forward-GEMM time (bench.py reports both lines).  Default one plane (the throughput mode);
-# MTTS_W_SPLIT=1 or set_weight_split(True) selects the split planes.
-_W_SPLIT = os.environ.get("MTTS_W_SPLIT", "0") == "1"
+# (tools/r3/precision_budget.py, last runnable at 3dd8270: prior 2.9e-4 / diff 2.1e-4 from weight rounding
+# alone, activations 3.8e-5 / 2.1e-5 at B=32) -- with split planes bf16-mixed meets the 1e-4 loss bar at the
+# bench batch, at ~+50 % forward-GEMM time (bench.py reports both lines).  Default one plane (the throughput
+# mode); set_weight_split(True) selects the split planes.
+_W_SPLIT = False
 
 
 GEMM_F_A_SPLIT = 0x80  # MTTS_GEMM_F_A_SPLIT: with W_SPLIT, fp32 A split into hi + lo planes (bf16x3)
@@ -71,7 +70,8 @@ GEMM_F_A_SPLIT = 0x80  # MTTS_GEMM_F_A_SPLIT: with W_SPLIT, fp32 A split into hi
 # operands (A_hi W_hi + A_hi W_lo + A_lo W_hi: ~16 significant bits per operand, fp32 accumulate) and the
 # attention forward runs exact fp32 MFMA; the backward of the same ops stays bf16 one-plane.  The
 # text encoder runs this way in the parity policy (MatchaTTS.encoder_precision = "bf16x3"): its
-# activations' bf16 rounding decides the alignment's near-ties (tools/r3/precision_budget.py).
+# activations' bf16 rounding decides the alignment's near-ties (tools/r3/precision_budget.py, last
+# runnable at 3dd8270).
 _PRECISE: contextvars.ContextVar = contextvars.ContextVar("mtts_precise_fwd", default=False)
 
 
@@ -118,9 +118,8 @@ def weight_split_enabled() -> bool:
 # most of any GEMM (the GELU epilogue pins it to the register schedule).  Measured (profiles/r04/ff1_one_plane/):
 # step 7.99 / 8.01 -> 7.85 / 7.86 ms; parity errors (prior, diff) B=4 vs the reference fixture 0 / 1.2e-5, B=32
 # 0 / 3.4e-7, 512 x 4096 1.9e-7 / 3.3e-5, alignment exact in all three.  MTTS_PARITY_FF1_SPLIT=1: split it too.
+# The down-projection (~3 % share) is always split under the policy (A/B last runnable at 3dd8270).
 _FF1_SPLIT = os.environ.get("MTTS_PARITY_FF1_SPLIT", "0") != "0"
-# MTTS_PARITY_FF2_SPLIT=0: the FF down-projection in one plane too (~3 % share; A/B only)
-_FF2_SPLIT = os.environ.get("MTTS_PARITY_FF2_SPLIT", "1") != "0"
 
 # the parity policy's text-encoder forward: "fp32fwd" (exact-fp32 MFMA: 32-true's arithmetic) or "bf16x6"
 # (three exact bf16 planes per operand, six MFMAs).  bf16x6 measured 8.16 vs 8.05 ms per step and 1-3x the
@@ -552,12 +551,7 @@ def _ld(t: torch.Tensor) -> int:
     return t.stride(-2)
 
 
-_ROW_STRIDED = os.environ.get("MTTS_ROW_STRIDED", "1") != "0"
-
-
 def _row_strided_f32(t: torch.Tensor) -> bool:
-    if not _ROW_STRIDED:
-        return False
     try:
         return t.dtype == torch.float32 and t.dim() == 3 and _ld(t) >= t.shape[-1]
     except ValueError:
@@ -620,7 +614,7 @@ def _gemm(A, Ti, To, nb, in_stride, offs, cin, Wp, Kp, N_, C, To_full, out_strid
     args.flags = ((GEMM_F_BINARY_SCALE if (binary_scale and a_scale is not None) else 0)
                   | (GEMM_F_A_BF16 if A.dtype == torch.bfloat16 else 0)
                   | (GEMM_F_C_BF16 if C.dtype == torch.bfloat16 else 0)
-                  | (GEMM_F_FAST_ACT if (prec == PREC_BF16 and _FAST_ACT) else 0)
+                  | (GEMM_F_FAST_ACT if prec == PREC_BF16 else 0)
                   | (GEMM_F_PRE_BF16 if any(t is not None and t.dtype == torch.bfloat16 for t in (C_pre, aux)) else 0)
                   | (GEMM_F_W_SPLIT if w_split else 0) | (GEMM_F_A_SPLIT if a_split else 0)
                   | (GEMM_F_SPLIT3 if split3 else 0))
@@ -992,6 +986,56 @@ class _LinearTM(torch.autograd.Function):
         return (dx, db, dres, None, None, None, None, *dws)
 
 
+def _ff_fwd(a, w1, b1, w2, b2, residual, dropout_p, prec, one_plane, dgrad):
+    """The FeedForward core both classes below run: y = residual + dropout(gelu(a W1^T + b1)) W2^T + b2 on the
+    rows a [M, K].  one_plane / dgrad are per weight, (w1, w2): never the split planes / pack the dgrad operand
+    too.  Returns y, the saved pre-activation z, the hidden rows, the dropout seed and the dgrad operands."""
+    M, K = a.shape
+    H, Nout = w1.shape[0], w2.shape[0]
+    W1p, K1p = packed(spec_linear((w1,), one_plane=one_plane[0]), prec)
+    W2p, K2p = packed(spec_linear((w2,), one_plane=one_plane[1]), prec)
+    w2t = packed(spec_linear((w2,), dgrad=True), prec) if dgrad[1] else None
+    w1t = packed(spec_linear((w1,), dgrad=True), prec) if dgrad[0] else None
+    # bf16-mixed: the GELU output is only ever the next GEMM's (and its wgrad's) bf16 MFMA operand,
+    # so it is stored as bf16 -- half the bytes written here and read twice later; the saved
+    # pre-activation (read once, by GELU' in the backward) too, as autocast would keep it
+    # (fp32 storage A/B last runnable at 3dd8270)
+    dt = torch.bfloat16 if prec == PREC_BF16 else torch.float32
+    z = torch.empty(M, H, device=a.device, dtype=dt)
+    hid = torch.empty(M, H, device=a.device, dtype=dt)
+    seed = _new_seed(a.device) if dropout_p > 0 else None
+    _gemm(a, M, M, 1, 1, [0], K, W1p, K1p, H, hid, M, prec=prec, bias=_f32c(b1), act=ACT_GELU, C_pre=z,
+          dropout_p=dropout_p, seed=seed)
+    y = torch.empty(M, Nout, device=a.device, dtype=torch.float32)
+    _gemm(hid, M, M, 1, 1, [0], H, W2p, K2p, Nout, y, M, prec=prec, bias=_f32c(b2), residual=residual)
+    return y, z, hid, seed, w1t, w2t
+
+
+def _ff_bwd(dy2, a, z, hid, w1s, w2s, w1t, w2t, keys, has_b, prec, p, seed, dz16, want_da, db_always):
+    """_ff_fwd's backward: dW2 / db2, d(pre-activation) (GELU' and the regenerated dropout mask in the dgrad
+    epilogue), dW1 / db1 and, if wanted, da.  keys / has_b: (w1, b1, w2, b2) slot keys / (b1, b2) present;
+    dz16: dz stored bf16; db_always: a bias gradient is computed (and dropped) for an absent bias too."""
+    M = dy2.shape[0]
+    H, K, Nout = w1s[0], w1s[1], w2s[0]
+    dev = dy2.device
+    kw1, kb1, kw2, kb2 = keys
+    dw2 = _grad_buf(kw2, w2s, dev)
+    db2 = _grad_buf(kb2, (Nout,), dev) if (has_b[1] or db_always) else None
+    _wgrad(dy2, M, 1, 0, hid, M, M, 1, 1, [0], H, Nout, dw2, (H, 1, 0), prec=prec, db=db2)
+    W2t, K2p = w2t
+    dz = torch.empty(M, H, device=dev, dtype=torch.bfloat16 if dz16 else torch.float32)
+    _gemm(dy2, M, M, 1, 1, [0], Nout, W2t, K2p, H, dz, M, prec=prec, act=ACT_DGELU, aux=z, dropout_p=p, seed=seed)
+    dw1 = _grad_buf(kw1, w1s, dev)
+    db1 = _grad_buf(kb1, (H,), dev) if (has_b[0] or db_always) else None
+    _wgrad(dz, M, 1, 0, a, M, M, 1, 1, [0], K, H, dw1, (K, 1, 0), prec=prec, db=db1)
+    da = None
+    if want_da:
+        W1t, K1p = w1t
+        da = torch.empty(M, K, device=dev, dtype=torch.float32)
+        _gemm(dz, M, M, 1, 1, [0], H, W1t, K1p, K, da, M, prec=prec)
+    return da, dw1, (db1 if has_b[0] else None), dw2, (db2 if has_b[1] else None)
+
+
 class _FeedForwardTM(torch.autograd.Function):
     """residual + dropout(gelu(x W1^T + b1)) W2^T + b2   (diffusers GELU -> Dropout -> Linear,
     transformer.py:155-188).  The pre-activation is stored by the first GEMM's epilogue; the backward
@@ -1003,25 +1047,10 @@ class _FeedForwardTM(torch.autograd.Function):
         prec = gemm_precision()
         shp = x.shape
         x2 = _f32c(x).reshape(-1, shp[-1])
-        M, K = x2.shape
-        H, Nout = w1.shape[0], w2.shape[0]
-        W1p, K1p = packed(spec_linear((w1,)), prec)
-        W2p, K2p = packed(spec_linear((w2,)), prec)
-        ctx.w2t = packed(spec_linear((w2,), dgrad=True), prec) if any(ctx.needs_input_grad) else None
-        ctx.w1t = packed(spec_linear((w1,), dgrad=True), prec) if ctx.needs_input_grad[0] else None
-        # bf16-mixed: the GELU output is only ever the next GEMM's (and its wgrad's) bf16 MFMA operand,
-        # so it is stored as bf16 -- half the bytes written here and read twice later; the saved
-        # pre-activation (read once, by GELU' in the backward) too, as autocast would keep it
-        h16 = prec == PREC_BF16 and os.environ.get("MTTS_FF_FP32_HIDDEN") != "1"
-        z16 = prec == PREC_BF16 and os.environ.get("MTTS_FF_FP32_PRE") != "1"
-        z = torch.empty(M, H, device=x.device, dtype=torch.bfloat16 if z16 else torch.float32)
-        h = torch.empty(M, H, device=x.device, dtype=torch.bfloat16 if h16 else torch.float32)
-        seed = _new_seed(x.device) if dropout_p > 0 else None
-        _gemm(x2, M, M, 1, 1, [0], K, W1p, K1p, H, h, M, prec=prec, bias=_f32c(b1), act=ACT_GELU, C_pre=z,
-              dropout_p=dropout_p, seed=seed)
-        y = torch.empty(M, Nout, device=x.device, dtype=torch.float32)
-        res2 = _f32c(residual).reshape(M, Nout) if residual is not None else None
-        _gemm(h, M, M, 1, 1, [0], H, W2p, K2p, Nout, y, M, prec=prec, bias=_f32c(b2), residual=res2)
+        Nout = w2.shape[0]
+        res2 = _f32c(residual).reshape(-1, Nout) if residual is not None else None
+        y, z, h, seed, ctx.w1t, ctx.w2t = _ff_fwd(x2, w1, b1, w2, b2, res2, dropout_p, prec, (False, False),
+                                                  (ctx.needs_input_grad[0], any(ctx.needs_input_grad)))
         ctx.save_for_backward(x2, z, h, w1, w2)
         ctx.leaf = _leaves(w1, b1, w2, b2)
         ctx.keys = (_pkey(w1), _pkey(b1), _pkey(w2), _pkey(b2))
@@ -1033,29 +1062,12 @@ class _FeedForwardTM(torch.autograd.Function):
     def backward(ctx, dy):
         x2, z, h, w1, w2 = ctx.saved_tensors
         prec, shp, has_res, p, seed, has_b1, has_b2 = ctx.cfg
-        H, K = w1.shape
-        Nout = w2.shape[0]
-        dy2 = _f32c(dy).reshape(-1, Nout)
-        M = dy2.shape[0]
-        dev = dy2.device
-        kw1, kb1, kw2, kb2 = ctx.keys
-        dw2 = _grad_buf(kw2, w2.shape, dev)
-        db2 = _grad_buf(kb2 if has_b2 else None, (Nout,), dev)
-        _wgrad(dy2, M, 1, 0, h, M, M, 1, 1, [0], H, Nout, dw2, (H, 1, 0), prec=prec, db=db2)
-        W2t, K2p = ctx.w2t
-        dz = torch.empty(M, H, device=dev, dtype=torch.float32)
-        _gemm(dy2, M, M, 1, 1, [0], Nout, W2t, K2p, H, dz, M, prec=prec, act=ACT_DGELU, aux=z, dropout_p=p,
-              seed=seed)
-        dw1 = _grad_buf(kw1, w1.shape, dev)
-        db1 = _grad_buf(kb1 if has_b1 else None, (H,), dev)
-        _wgrad(dz, M, 1, 0, x2, M, M, 1, 1, [0], K, H, dw1, (K, 1, 0), prec=prec, db=db1)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            W1t, K1p = ctx.w1t
-            dx = torch.empty(M, K, device=dev, dtype=torch.float32)
-            _gemm(dz, M, M, 1, 1, [0], H, W1t, K1p, K, dx, M, prec=prec)
-            dx = dx.reshape(*shp)
-        return (dx, dw1, db1 if has_b1 else None, dw2, db2 if has_b2 else None, (dy if has_res else None),
+        dy2 = _f32c(dy).reshape(-1, w2.shape[0])
+        # dz fp32 and a bias-gradient buffer whatever the bias: as this op has always run
+        dx, dw1, db1, dw2, db2 = _ff_bwd(dy2, x2, z, h, w1.shape, w2.shape, ctx.w1t, ctx.w2t, ctx.keys,
+                                         (has_b1, has_b2), prec, p, seed, dz16=False,
+                                         want_da=ctx.needs_input_grad[0], db_always=True)
+        return ((dx.reshape(*shp) if dx is not None else None), dw1, db1, dw2, db2, (dy if has_res else None),
                 None)
 
 
@@ -1447,12 +1459,6 @@ def attention_tm(qkv, key_bias, heads: int, dropout_p: float = 0.0):
 # LayerNorm backward (mtts_layernorm_bwd_res) instead of an autograd accumulate kernel per sub-block.
 N.register("mtts_layernorm_bwd_res", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _SZ, _P])
 NORM_F_Y_BF16 = 0x100  # include/mtts_decoder.h MTTS_NORM_F_Y_BF16
-_PRELN_N16 = os.environ.get("MTTS_PRELN_N16", "1") != "0"  # attention block's LN output as bf16 (A/B switch)
-_ATTN_IO16 = os.environ.get("MTTS_ATTN_IO16", "1") != "0"  # bf16 q|k|v / o / dO / dq|dk|dv (A/B switch)
-# the FeedForward block's LN output as bf16 (round 5; same-box step A/B 7.546 / 7.531 -> 7.465 / 7.456 ms, bitwise
-# the same losses, profiles/r05/ab_preln_ff_n16.txt): the up-projection (now the weight-stationary
-# kernel, which rounds an fp32 A to bf16 at the fragment read anyway) and dW1 read it
-_PRELN_FF_N16 = os.environ.get("MTTS_PRELN_FF_N16", "1") != "0"
 
 
 def _ln_fwd(h2, w, b, eps, y16):
@@ -1494,15 +1500,17 @@ class _PreLNAttentionTM(torch.autograd.Function):
         M, C = h2.shape
         B, T = shp[0], shp[1]
         lnw, lnb = _f32c(ln_w), _f32c(ln_b)
-        # (not under precise_forward: its bf16x3 / fp32 GEMMs read the fp32 A's low bits -- ADVICE r5)
-        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, prec == PREC_BF16 and _PRELN_N16 and not _PRECISE.get())
+        # bf16-mixed: the LN output is only the q|k|v projection's A operand -- stored bf16 (A/B last runnable at
+        # 3dd8270; not under precise_forward: its bf16x3 / fp32 GEMMs read the fp32 A's low bits -- ADVICE r5)
+        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, prec == PREC_BF16 and not _PRECISE.get())
         Wqkv, Kq = packed(spec_linear((wq, wk, wv)), prec)
         Wo, Ko = packed(spec_linear((w_out,)), prec)
         ctx.wqkv_t = packed(spec_linear((wq, wk, wv), dgrad=True), prec)
         ctx.wo_t = packed(spec_linear((w_out,), dgrad=True), prec)
         C3 = 3 * wq.shape[0]
-        # bf16-mixed: q|k|v and o are only MFMA operands (attention, to_out) -- stored bf16
-        io16 = prec == PREC_BF16 and _ATTN_IO16 and _bf16_operand_ok(C3 // 3)
+        # bf16-mixed: q|k|v and o (and dO, dq|dk|dv) are only MFMA operands (attention, to_out) -- stored bf16
+        # (A/B last runnable at 3dd8270)
+        io16 = prec == PREC_BF16 and _bf16_operand_ok(C3 // 3)
         adt = torch.bfloat16 if io16 else torch.float32
         qkv = torch.empty(B, T, C3, device=h.device, dtype=adt)
         _gemm(n, M, M, 1, 1, [0], C, Wqkv, Kq, C3, qkv.view(M, C3), M, prec=prec)
@@ -1568,26 +1576,15 @@ class _PreLNFeedForwardTM(torch.autograd.Function):
         prec = gemm_precision()
         shp = h.shape
         h2 = _f32c(h).reshape(-1, shp[-1])
-        M, C = h2.shape
-        H = w1.shape[0]
         lnw, lnb = _f32c(ln_w), _f32c(ln_b)
-        # bf16 LayerNorm output (round 5, _PRELN_FF_N16): the GELU up-projection runs on the weight-stationary
-        # kernel, which rounds an fp32 A to bf16 at its fragment read anyway -- the same products, half the bytes
-        # (rounds 2-4 kept it fp32: the register-staged schedule then hid the GELU epilogue better)
+        # bf16 LayerNorm output (round 5; same-box step A/B 7.546 / 7.531 -> 7.465 / 7.456 ms, bitwise the same
+        # losses, profiles/r05/ab_preln_ff_n16.txt; A/B last runnable at 3dd8270): the GELU up-projection runs on
+        # the weight-stationary kernel, which rounds an fp32 A to bf16 at its fragment read anyway -- the same
+        # products, half the bytes, and dW1 reads it too
         # (not under precise_forward, whose split-A GEMMs need the fp32 LN output -- ADVICE r5)
-        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, prec == PREC_BF16 and _PRELN_FF_N16 and not _PRECISE.get())
-        W1p, K1p = packed(spec_linear((w1,), one_plane=not _FF1_SPLIT), prec)
-        W2p, K2p = packed(spec_linear((w2,), one_plane=not _FF2_SPLIT), prec)
-        ctx.w2t = packed(spec_linear((w2,), dgrad=True), prec)
-        ctx.w1t = packed(spec_linear((w1,), dgrad=True), prec)
-        b16 = prec == PREC_BF16
-        z = torch.empty(M, H, device=h.device, dtype=torch.bfloat16 if b16 else torch.float32)  # pre-activation
-        hid = torch.empty(M, H, device=h.device, dtype=torch.bfloat16 if b16 else torch.float32)
-        seed = _new_seed(h.device) if dropout_p > 0 else None
-        _gemm(n, M, M, 1, 1, [0], C, W1p, K1p, H, hid, M, prec=prec, bias=_f32c(b1), act=ACT_GELU, C_pre=z,
-              dropout_p=dropout_p, seed=seed)
-        y = torch.empty(M, C, device=h.device, dtype=torch.float32)
-        _gemm(hid, M, M, 1, 1, [0], H, W2p, K2p, C, y, M, prec=prec, bias=_f32c(b2), residual=h2)
+        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, prec == PREC_BF16 and not _PRECISE.get())
+        y, z, hid, seed, ctx.w1t, ctx.w2t = _ff_fwd(n, w1, b1, w2, b2, h2, dropout_p, prec,
+                                                    (not _FF1_SPLIT, False), (True, True))
         ctx.save_for_backward(h2, lnw, lnb, mean, rstd, n, z, hid)
         ctx.leaf = _leaves(ln_w, ln_b, w1, b1, w2, b2)
         ctx.keys = tuple(_pkey(t) for t in (ln_w, ln_b, w1, b1, w2, b2))
@@ -1599,25 +1596,12 @@ class _PreLNFeedForwardTM(torch.autograd.Function):
     def backward(ctx, dy):
         h2, lnw, lnb, mean, rstd, n, z, hid = ctx.saved_tensors
         prec, shp, p, seed, w1s, w2s, has_b1, has_b2 = ctx.cfg
-        M, C = h2.shape
-        H = w1s[0]
-        dev = h2.device
-        dy2 = _f32c(dy).reshape(M, C)  # also the residual branch's gradient
-        klw, klb, kw1, kb1, kw2, kb2 = ctx.keys
-        dw2 = _grad_buf(kw2, w2s, dev)
-        db2 = _grad_buf(kb2, (C,), dev) if has_b2 else None
-        _wgrad(dy2, M, 1, 0, hid, M, M, 1, 1, [0], H, C, dw2, (H, 1, 0), prec=prec, db=db2)
-        W2t, K2p = ctx.w2t
+        dy2 = _f32c(dy).reshape(h2.shape)  # also the residual branch's gradient
         # d(pre-activation): bf16 in bf16-mixed -- only the next dgrad GEMM and dW1 read it
-        dz = torch.empty(M, H, device=dev, dtype=torch.bfloat16 if prec == PREC_BF16 else torch.float32)
-        _gemm(dy2, M, M, 1, 1, [0], C, W2t, K2p, H, dz, M, prec=prec, act=ACT_DGELU, aux=z, dropout_p=p, seed=seed)
-        dw1 = _grad_buf(kw1, w1s, dev)
-        db1 = _grad_buf(kb1, (H,), dev) if has_b1 else None
-        _wgrad(dz, M, 1, 0, n, M, M, 1, 1, [0], C, H, dw1, (C, 1, 0), prec=prec, db=db1)
-        W1t, K1p = ctx.w1t
-        dn = torch.empty(M, C, device=dev, dtype=torch.float32)
-        _gemm(dz, M, M, 1, 1, [0], H, W1t, K1p, C, dn, M, prec=prec)
-        dh, dlnw, dlnb = _ln_bwd_res(dn, h2, lnw, lnb, mean, rstd, dy2, (klw, klb))
+        dn, dw1, db1, dw2, db2 = _ff_bwd(dy2, n, z, hid, w1s, w2s, ctx.w1t, ctx.w2t, ctx.keys[2:],
+                                         (has_b1, has_b2), prec, p, seed, dz16=prec == PREC_BF16,
+                                         want_da=True, db_always=False)
+        dh, dlnw, dlnb = _ln_bwd_res(dn, h2, lnw, lnb, mean, rstd, dy2, ctx.keys[:2])
         return dh.reshape(shp), dlnw, dlnb, None, dw1, db1, dw2, db2, None
 
 

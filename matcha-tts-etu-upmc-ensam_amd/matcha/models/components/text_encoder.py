@@ -23,7 +23,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -32,10 +31,9 @@ from matcha import _native as N
 from matcha.models.components import _defer as D
 from matcha.models.components import _ops as O
 
-# MTTS_ENCODER_DX_LINK=0: autograd sums each encoder layer's two input gradients (A/B switch)
-_ENC_LINK = os.environ.get("MTTS_ENCODER_DX_LINK", "1") != "0"
-# MTTS_QKV_BIAS_ONE_CAT=0: one q|k|v bias concatenation per layer (A/B switch)
-_ONE_BIAS_CAT = os.environ.get("MTTS_QKV_BIAS_ONE_CAT", "1") != "0"
+# False: autograd sums each encoder layer's two input gradients.  A test seam, not an environment switch:
+# tests/test_encoder_ops_gpu.py flips this attribute to compare both sides.
+_ENC_LINK = True
 
 
 class ConvReluNorm(nn.Module):
@@ -206,13 +204,11 @@ class Encoder(nn.Module):
         p = self.dropout_rate if self.training else 0.0
         if key_bias is None:
             key_bias = (m - 1.0) * 1e4  # masked_fill(-1e4) on padded keys
-        # every layer's stacked q|k|v bias from ONE concatenation (one launch instead of one per layer)
+        # every layer's stacked q|k|v bias from ONE concatenation (one launch instead of one per layer; A/B last
+        # runnable at 3dd8270)
         layers = list(self.attention_layers)
-        if not _ONE_BIAS_CAT:
-            qkv_biases = [None] * len(layers)
-        else:
-            qkv_biases = torch.cat([b for a in layers for b in (a.query_conv.bias, a.key_conv.bias, a.value_conv.bias)])
-            qkv_biases = qkv_biases.split([3 * a.query_conv.bias.numel() for a in layers])
+        qkv_biases = torch.cat([b for a in layers for b in (a.query_conv.bias, a.key_conv.bias, a.value_conv.bias)])
+        qkv_biases = qkv_biases.split([3 * a.query_conv.bias.numel() for a in layers])
         for attn, ln1, ffn, ln2, qb in zip(layers, self.norm_layers_1, self.ffn_layers, self.norm_layers_2, qkv_biases):
             # h feeds the masked q|k|v projection and output_conv's residual: the residual gradient is added in
             # the projection's dgrad epilogue ((acc + g) * m; g vanishes on masked rows: it is LN1's input

@@ -11,16 +11,12 @@ Token-major forward (``forward_tm``): the q/k/v projections run as ONE GEMM agai
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from matcha.models.components import _ops as O
-
-# MTTS_PRELN_FUSED=0: BasicTransformerBlock.forward_tm runs op by op (A/B measurements)
-_PRELN_FUSED = os.environ.get("MTTS_PRELN_FUSED", "1") != "0"
 
 
 class GELU(nn.Module):
@@ -77,11 +73,11 @@ class Attention(nn.Module):
     def qkv_weight(self):
         return torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight], dim=0)
 
-    def forward_tm(self, h, key_bias, residual=None):
+    def forward_tm(self, h, key_bias):
         qkv = O.linear_tm(h, (self.to_q.weight, self.to_k.weight, self.to_v.weight), None)  # [B,T,3C] q|k|v
         o = O.attention_tm(qkv, key_bias, self.heads)
         p = self.to_out[1].p if self.training else 0.0
-        return O.linear_tm(o, self.to_out[0].weight, self.to_out[0].bias, residual=residual, dropout_p=p)
+        return O.linear_tm(o, self.to_out[0].weight, self.to_out[0].bias, dropout_p=p)
 
     def forward(self, hidden_states, encoder_hidden_states=None, attention_mask=None, **kw):
         if encoder_hidden_states is not None:
@@ -111,13 +107,9 @@ class BasicTransformerBlock(nn.Module):
 
     def forward_tm(self, h, key_bias):
         """h [B, T, C]; key_bias [B, T] (the reference's float mask).  Each pre-LN residual sub-block is
-        one fused op (components/_ops.py preln_attention_tm / preln_ff_tm)."""
+        one fused op (components/_ops.py preln_attention_tm / preln_ff_tm; the op-by-op composition they were
+        measured against was last runnable at 3dd8270)."""
         a, ff = self.attn1, self.ff
-        if not _PRELN_FUSED:  # op-by-op composition (A/B measurements)
-            n = O.layer_norm_tm(h, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-            h = a.forward_tm(n, key_bias, residual=h)
-            n = O.layer_norm_tm(h, self.norm3.weight, self.norm3.bias, self.norm3.eps)
-            return ff.forward_tm(n, residual=h)
         h = O.preln_attention_tm(h, self.norm1.weight, self.norm1.bias, self.norm1.eps, key_bias, a.heads,
                                  a.to_q.weight, a.to_k.weight, a.to_v.weight, a.to_out[0].weight, a.to_out[0].bias,
                                  dropout_p=a.to_out[1].p if self.training else 0.0)

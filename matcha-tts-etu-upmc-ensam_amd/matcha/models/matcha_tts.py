@@ -179,8 +179,8 @@ class MatchaTTS(BaseLightningClass):
         # the text encoder runs on the same HIP GEMM/attention kernels as the decoder and follows the
         # caller's precision (bf16 MFMA operands inside a bf16 autocast region) unless encoder_precision says
         # otherwise: "bf16x3" / "fp32" take its activations' bf16 rounding -- what is left of the bf16 prior-loss
-        # error and every alignment flip once the weights enter as split planes (tools/r3/precision_budget.py)
-        # -- out of the forward
+        # error and every alignment flip once the weights enter as split planes (tools/r3/precision_budget.py,
+        # last runnable at 3dd8270) -- out of the forward
         # inside a Trainer step (the gradient deferral's side stream exists): the decoder's weight packs and
         # time path for this step's CFM time run on the side stream beside the text encoder (t drawn here
         # instead of in compute_loss; the same distribution)
@@ -196,15 +196,17 @@ class MatchaTTS(BaseLightningClass):
         y_max_length = y.shape[-1]
         y_mask = O.sequence_mask_f32(y_lengths, y_max_length).unsqueeze(1)  # sequence_mask(...).to(x_mask), one launch
         runs = None
+        # MTTS_SEGMENT_HOST=1 (read per call: a test flips it): the reference's host-side paths
+        on_dev = x.is_cuda and os.environ.get("MTTS_SEGMENT_HOST", "0") != "1"
         # out_size on the device: the window is cut from the runs, the dense [B,Tx,Ty] path is never written
-        crop_dev = out_size is not None and x.is_cuda and os.environ.get("MTTS_SEGMENT_HOST", "0") != "1"
+        crop_dev = out_size is not None and on_dev
         # what the forward crop windows on: (t_x, t_y); the runs carry what ends the last row's run (the same for MAS)
         lens = None
         if self.use_precomputed_durations:
             if durations is None:
                 raise ValueError("use_precomputed_durations=True: forward needs `durations` ([B,Tx] or [B,1,Tx], "
                                  "e.g. MatchaTTS.align's)")
-            if x.is_cuda and os.environ.get("MTTS_SEGMENT_HOST", "0") != "1":
+            if on_dev:
                 # :273-274 on runs (monotonic_align.duration_path): one launch instead of generate_path's cumsum,
                 # [B*Tx,Ty] mask and elementwise passes; the consumers below are the MAS branch's
                 with torch.no_grad():

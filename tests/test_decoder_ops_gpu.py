@@ -647,8 +647,8 @@ def test_grad_link_two_consumers(stride):
 
 def test_decoder_grad_links_match_autograd_sums():
     """The decoder with its GradLinks (Resnet1D inputs, skip / concat) vs the same decoder with autograd
-    summing the input gradients (MTTS_RESNET_DX_LINK=0 path): same loss, same parameter gradients (fp32
-    mode; the fused sums differ from autograd's only in the sign of masked zeros)."""
+    summing the input gradients (the module attribute decoder._DX_LINK = False): same loss, same parameter
+    gradients (fp32 mode; the fused sums differ from autograd's only in the sign of masked zeros)."""
     from matcha.models.components import decoder as D
 
     torch.manual_seed(11)

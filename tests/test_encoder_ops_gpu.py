@@ -236,7 +236,7 @@ def test_embedding_fwd_bitwise_bwd_deterministic(B, T, V, C):
 def test_encoder_grad_link_matches_autograd_sum():
     """Each encoder layer's output_conv residual gradient is added in the masked q|k|v projection's dgrad
     epilogue (GradLink) instead of autograd's add: same losses and gradients as with autograd summing
-    them (MTTS_ENCODER_DX_LINK=0 path), fp32 mode, ragged lengths (the masked rows are where the
+    them (the module attribute text_encoder._ENC_LINK = False), fp32 mode, ragged lengths (the masked rows are where the
     (acc + g) * m identity needs g = 0)."""
     from matcha.models.components import text_encoder as TE
     from matcha.models.matcha_tts import MatchaTTS

@@ -9,7 +9,8 @@ precisions.
 32-true: alignment bit-exact, each loss within 1e-4 relative (the north star's bar).
 bf16-parity (the bench default since round 4): bf16-mixed with split bf16 weight planes
 (MTTS_GEMM_F_W_SPLIT: the fp32 weights' static rounding -- the dominant bf16 loss error, tools/r3/
-precision_budget.py -- drops out) and the text encoder's FORWARD on the exact-fp32 MFMA with fp32 weights
+precision_budget.py, last runnable at 3dd8270 -- drops out) and the text encoder's FORWARD on the exact-fp32
+MFMA with fp32 weights
 (precise_forward("fp32"): 32-true's forward arithmetic), backward bf16: the encoder's activation rounding
 decided every alignment near-tie.  Bar: alignment bit-exact and every loss (duration included) within 1e-4
 relative.  bf16-parity-fp32enc: round 3's policy (the whole encoder in exact fp32, backward too), same bar.

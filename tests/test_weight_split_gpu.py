@@ -1,8 +1,8 @@
 """bf16-mixed forward GEMMs with split weight planes (MTTS_GEMM_F_W_SPLIT, csrc/pack.hip +
 conv_gemm*.hip): the fp32 weights enter as hi = bf16(w) and lo = bf16(w - hi), two MFMAs per product,
 so the only rounding left is the activations' (a per-sample, zero-mean error) -- the static weight
-rounding was the bf16 loss error (tools/r3/precision_budget.py).  Checked against float64 on bf16-exact
-activations and UNROUNDED fp32 weights, on each schedule family the forward uses: the LDS-DMA kernels
+rounding was the bf16 loss error (tools/r3/precision_budget.py, last runnable at 3dd8270).  Checked against
+float64 on bf16-exact activations and UNROUNDED fp32 weights, on each schedule family the forward uses: the LDS-DMA kernels
 (fp32 and bf16 A, 64 x 64 and 64 x 256 tiles, split-K), the register-staged GELU schedule."""
 from __future__ import annotations
 
@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 # bf16 activations, split weights: relative error of the residual's own rounding (2^-17 of w) plus fp32
-# accumulation -- about 1e-5 of the output scale; one plane (MTTS_W_SPLIT=0) gives ~3e-3
+# accumulation -- about 1e-5 of the output scale; one plane (set_weight_split(False)) gives ~3e-3
 TOL = 3e-5
 
 
