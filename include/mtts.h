@@ -23,6 +23,9 @@
  *                                     (bound as maximum_path_c, __init__.py:4-8)
  *   mtts_losses_fwd / _bwd         <- flow_matching.py:145-149 (CFM loss) + matcha_tts.py:319-323 (prior loss)
  *   mtts_mel_log_fwd               <- matcha/utils/audio_process.py:62-72  MelSpectrogram.__call__ (after the STFT)
+ *   mtts_mel_from_wav              <- matcha/utils/audio_process.py:45-72 per utterance + ljspeech_datamodule.py:84-109
+ *                                     (the padded mel batch and y_lengths), from the waveforms in one launch
+ *   mtts_mel_stats                 <- the sums of upstream's data-statistics script (mel_mean, mel_std)
  *   mtts_sequence_mask_f32         <- matcha/utils/model.py:13-34 sequence_mask(...).to(float) (matcha_tts.py:259,
  *                                     text_encoder.py:398) and text_encoder.py:300-303 masked_fill(-1e4) as a key bias
  *   mtts_duration_loss_fwd / _bwd  <- matcha_tts.py:287-288 + utils/model.py:117-135 duration_loss
@@ -198,6 +201,39 @@ int mtts_segment_crop_bwd(const float *d_mu_y_cut, const int32_t *row_start, con
 int mtts_mel_log_fwd(const float *spec, const float *mel_w, const int32_t *band_lo, const int32_t *band_hi,
                      int32_t B, int32_t n_freq, int32_t F, int32_t n_mels, float clip_val, float *out,
                      void *hip_stream);
+
+/*
+ * The whole front end in one launch: a ragged waveform batch -> padded log-mel and frame counts, each utterance
+ * computed on its own waveform (the reference runs MelSpectrogram per utterance and collate zero-pads the mels).
+ *   wav        : [B, L] float32 in [-1, 1], or int16 when wav_is_int16 != 0 (converted as float(s) / 32768, exact)
+ *   lengths    : int32 [B] on the device, samples per row; NULL: every row has L.  Clamped to [0, L] by the kernel:
+ *                it may hold anything, and no sample outside [0, len) of a row is read.
+ *   mel_w, band_lo, band_hi : as for mtts_mel_log_fwd, mel_w [n_mels, 513]
+ *   twiddle    : float32 [1024, 2], exp(-2 pi i k / 1024); window: float32 [1024] (periodic Hann); both 8-byte aligned
+ *   n_fft = win_size = 1024, hop = 256 is the one geometry served (center=False with the reference's manual reflect
+ *   pad of 384 per side); anything else returns MTTS_ERR_SHAPE before any launch.  B <= 65535, n_mels <= 96, L <= 2^30.
+ *   out        : float32 [B, n_mels, F_out], F_out = L / 256, fully written.  With len = clamp(lengths[b], 0, L) and
+ *                F_b = len / 256 if len >= 385 (the shortest waveform a reflect pad by 384 accepts) else 0:
+ *                  f <  F_b: (log(max(sum_k mel_w[m,k] * sqrt(re^2 + im^2 + 1e-9), clip_val)) - mean) / std of the
+ *                            spectrum of window * x_pad[256 f : 256 f + 1024], x_pad the utterance's own reflect-padded
+ *                            signal; the division is a true division (mean = 0, std = 1 change no bit)
+ *                  f >= F_b: pad_value exactly
+ *   mel_lengths: int32 [B] output, F_b.  Written also when F_out == 0.
+ * Deterministic (no atomics, fixed summation order); a row's result does not depend on the other rows.
+ */
+int mtts_mel_from_wav(const void *wav, int32_t wav_is_int16, const int32_t *lengths, const float *mel_w,
+                      const int32_t *band_lo, const int32_t *band_hi, const float *twiddle, const float *window,
+                      int32_t B, int32_t L, int32_t n_fft, int32_t win_size, int32_t hop, int32_t n_mels,
+                      float clip_val, float mean, float std, float pad_value, float *out, int32_t *mel_lengths,
+                      void *hip_stream);
+
+/*
+ * stats[b] = (sum v, sum v^2) in float64 over mel[b, :, :mel_lengths[b]]  (the sums behind data_statistics).
+ *   mel: float32 [B, n_mels, F]; mel_lengths: int32 [B] on the device, clamped to [0, F]; stats: float64 [B, 2].
+ *   One launch, no atomics, a fixed summation order.
+ */
+int mtts_mel_stats(const float *mel, const int32_t *mel_lengths, int32_t B, int32_t n_mels, int32_t F, double *stats,
+                   void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training losses (flow_matching.py:145-149 CFM loss, matcha_tts.py:319-323 prior loss), fused

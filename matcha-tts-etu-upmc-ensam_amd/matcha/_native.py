@@ -51,6 +51,9 @@ _SIGNATURES: dict[str, tuple] = {
     "mtts_cfm_pack_bwd": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
     "mtts_time_embedding": (ctypes.c_int, [_P, _I32, _I32, _F, _P, _P]),
     "mtts_mel_log_fwd": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _P]),
+    "mtts_mel_from_wav": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F,
+                                         _F, _F, _P, _P, _P]),
+    "mtts_mel_stats": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     # (args, precision, tile_cfg, splits, out[6]) -> schedule id, splits, workgroups, resident per CU, rounds, fill
     "mtts_conv_gemm_plan": (ctypes.c_int, [_P, _I32, _I32, _I32, ctypes.POINTER(_I32 * 6)]),
     "mtts_conv_gemm_glds_occupancy": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_I32 * 2)]),

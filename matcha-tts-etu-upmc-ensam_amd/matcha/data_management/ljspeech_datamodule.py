@@ -10,7 +10,8 @@ utterance of every length stratum (balanced padded T, identical batch counts on 
 Bucketing changes what the decoder sees (GroupNorm statistics run over the padded T, decoder.py:58-66),
 so the reference's unbucketed order stays available: `shuffle=True, bucket_batches=0`.
 The file-reading Dataset (text cleaners + wav IO) is not on the hot path; MelSpectrogram
-(matcha/utils/audio_process.py) computes the features on the GPU in batch.
+(matcha/utils/audio_process.py) computes the features on the GPU in batch: `collate_wav(batch)` pads the
+int16 waveforms instead of mels, and `MelSpectrogram.batch(wav, wav_lengths)` turns them into `y` / `y_lengths`.
 """
 from __future__ import annotations
 
@@ -51,6 +52,36 @@ def collate(batch, x_quantum: int = 1, y_quantum: int = 1, n_vocab: int | None =
     if ty != y_padded.shape[2]:
         y_padded = torch.nn.functional.pad(y_padded, (0, ty - y_padded.shape[2]))
     return {"x": x_padded, "x_lengths": x_lengths, "y": y_padded, "y_lengths": y_lengths}
+
+
+def collate_wav(batch, x_quantum: int = 1, wav_quantum: int = 256, n_vocab: int | None = None):
+    """Batch assembly for features computed on the device: items {"x": int64 [Tx_i], "x_lengths", "wav": int16 [L_i]}
+    -> {"x" [B, Tx_max] int64, "x_lengths" [B], "wav" int16 [B, L_max], "wav_lengths" [B]}, zero-padded; x, x_quantum
+    and n_vocab as in `collate`.  L_max is rounded up to a multiple of wav_quantum (default: one hop, so the padded
+    row holds a whole number of frames; a larger quantum bounds the number of padded shapes as y_quantum does).
+    Loader workers then only read files: `MelSpectrogram.batch(wav.to(device), wav_lengths)` yields the y / y_lengths
+    the Trainer takes, each utterance's mel computed on its own waveform."""
+    if x_quantum < 1 or wav_quantum < 1:
+        raise ValueError(f"collate_wav: quanta must be positive, got {x_quantum}, {wav_quantum}")
+    x = [item["x"] for item in batch]
+    if n_vocab is not None:
+        for i, xi in enumerate(x):
+            if xi.numel() and (int(xi.min()) < 0 or int(xi.max()) >= n_vocab):
+                raise ValueError(f"collate_wav: item {i} has token ids outside [0, {n_vocab})")
+    wavs = [torch.as_tensor(item["wav"]) for item in batch]
+    for i, w in enumerate(wavs):
+        if w.dtype != torch.int16 or w.dim() != 1:
+            raise ValueError(f"collate_wav: item {i} wav must be int16 [L], got {w.dtype} {tuple(w.shape)}")
+    x_lengths = torch.tensor([int(item["x_lengths"]) for item in batch])
+    wav_lengths = torch.tensor([w.numel() for w in wavs])
+    x_padded = pad_sequence(x, batch_first=True, padding_value=0)
+    wav_padded = pad_sequence(wavs, batch_first=True, padding_value=0)
+    tx, tl = _round_up(x_padded.shape[1], x_quantum), _round_up(wav_padded.shape[1], wav_quantum)
+    if tx != x_padded.shape[1]:
+        x_padded = torch.nn.functional.pad(x_padded, (0, tx - x_padded.shape[1]))
+    if tl != wav_padded.shape[1]:
+        wav_padded = torch.nn.functional.pad(wav_padded, (0, tl - wav_padded.shape[1]))
+    return {"x": x_padded, "x_lengths": x_lengths, "wav": wav_padded, "wav_lengths": wav_lengths}
 
 
 class LengthBucketBatchSampler(torch.utils.data.Sampler):

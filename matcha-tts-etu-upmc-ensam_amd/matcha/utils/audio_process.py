@@ -1,8 +1,17 @@
-"""Log-mel features (reference: matcha/utils/audio_process.py:1-81), with the post-STFT chain on the
-MI355X: torch.stft (rocFFT) produces the complex spectrum in HBM, then ONE HIP kernel
-(csrc/mel.hip, mtts_mel_log_fwd) forms the magnitude sqrt(re^2+im^2+1e-9), projects it on the
-band-sparse slaney mel basis and applies log(clamp(., 1e-5)) -- the magnitude tensor and the matmul
-output never round-trip through HBM.
+"""Log-mel features (reference: matcha/utils/audio_process.py:1-81) on the MI355X, two ways.
+
+MelSpectrogram.batch(y, lengths): the whole front end in ONE HIP launch (csrc/mel_fused.hip, mtts_mel_from_wav) --
+a zero-padded batch of int16 or fp32 waveforms and their lengths in, the padded log-mel batch and its frame counts
+out.  Each utterance is reflect-padded at its own end, windowed, transformed (the 1024-point FFT of csrc/gl_fft.h in
+LDS), projected on the band-sparse slaney basis and logged as the reference does on that utterance alone; exact zeros
+follow its last frame, as collate pads; (mel - mel_mean) / mel_std is applied in the kernel on request.  Serves
+n_fft = win_size = 1024, hop_size = 256, center=False.  MelStatistics accumulates the data_statistics
+(mel_mean, mel_std) of a dataset from such batches on the device (mtts_mel_stats).
+
+MelSpectrogram.__call__(y): torch.stft (rocFFT) produces the complex spectrum in HBM, then one HIP kernel
+(csrc/mel.hip, mtts_mel_log_fwd) forms the magnitude sqrt(re^2+im^2+1e-9), projects it and applies
+log(clamp(., 1e-5)).  Any geometry, but fp32 only, and it pads at the end of the padded row: right for rows of one
+length (one call per utterance), wrong in the last frames of every shorter utterance of a padded batch.
 
 Same names and argument meaning as the reference: MelSpectrogram(n_fft, num_mels, sampling_rate,
 hop_size, win_size, fmin, fmax, center=False), __call__(y [B, T] float in [-1, 1]) -> [B, num_mels, F];
@@ -127,9 +136,124 @@ class MelSpectrogram:
         N.check(rc, "mtts_mel_log_fwd")
         return out
 
+    def _check_served(self):
+        if (self.n_fft, self.win_size, self.hop_size) != (GL_NFFT, GL_NFFT, GL_HOP) or self.center or \
+                not 1 <= self.num_mels <= 96:
+            raise ValueError(f"MelSpectrogram.batch serves n_fft = win_size = {GL_NFFT}, hop_size = {GL_HOP}, "
+                             f"center=False and num_mels <= 96 only, got n_fft={self.n_fft}, win_size={self.win_size}, "
+                             f"hop_size={self.hop_size}, center={self.center}, num_mels={self.num_mels}")
+
+    def batch(self, y, lengths=None, *, mel_mean=0.0, mel_std=1.0):
+        """Padded waveform batch -> (log-mel [B, num_mels, L // 256] float32, mel_lengths int64 [B]) in one launch
+        (mtts_mel_from_wav), each utterance computed on its own waveform as the reference's per-utterance call does:
+        reflect-padded at its own end, ``mel_lengths[b] = lengths[b] // 256`` frames, exact zeros after them (what
+        ``collate`` pads with).  ``(mel - mel_mean) / mel_std`` is applied to the valid frames inside the kernel; the
+        defaults change no bit.
+
+        y: [B, L] float32 in [-1, 1] or int16 (converted in the kernel as s / 32768), on the device.  lengths: samples
+        per row, or None for L everywhere.  A device int tensor is converted on the device and the call does no
+        host synchronisation (the kernel clamps it to [0, L]; a row shorter than 385 samples, the least a reflect
+        pad by 384 accepts, gets mel_lengths 0 and zeros); a host tensor or list is validated (ValueError below 385 or
+        above L) and copied.  With device lengths the call can be captured into an outer graph after one warm-up
+        call."""
+        self._check_served()
+        if not isinstance(y, torch.Tensor) or y.dim() != 2:
+            raise ValueError(f"MelSpectrogram.batch expects y [B, L], got {tuple(getattr(y, 'shape', ()))}")
+        if y.dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"MelSpectrogram.batch takes float32 or int16 waveforms, got {y.dtype}")
+        if not float(mel_std) > 0.0:
+            raise ValueError(f"mel_std must be positive, got {mel_std}")
+        B, L = y.shape
+        if B > 65535:
+            raise ValueError(f"MelSpectrogram.batch serves B <= 65535, got {B}")
+        if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
+            host = torch.as_tensor(lengths).reshape(-1)
+            if host.is_floating_point() or host.numel() != B:
+                raise ValueError(f"lengths must be {B} integers, got {host.dtype} x {host.numel()}")
+            if B and (int(host.min()) < MEL_MIN_SAMPLES or int(host.max()) > L):
+                raise ValueError(f"lengths must lie in [{MEL_MIN_SAMPLES}, L = {L}] (a reflect pad by "
+                                 f"{MEL_MIN_SAMPLES - 1} needs {MEL_MIN_SAMPLES} samples), got {int(host.min())} .. "
+                                 f"{int(host.max())}")
+            N.require_device(y)
+            lengths = host.to(torch.int32).to(y.device)
+        N.require_device(y, lengths)
+        if lengths is not None:
+            if lengths.dim() != 1 or lengths.numel() != B or lengths.is_floating_point():
+                raise ValueError(f"lengths must be an integer tensor [{B}], got {lengths.dtype} {tuple(lengths.shape)}")
+            lengths = lengths.to(torch.int32).contiguous()
+        y = y.contiguous()
+        basis, lo, hi, _ = self._buffers(y.device)
+        tw, win = _gl_device_tables(y.device)
+        out = torch.empty((B, self.num_mels, L // GL_HOP), dtype=torch.float32, device=y.device)
+        mel_lengths = torch.empty((B,), dtype=torch.int32, device=y.device)
+        with torch.cuda.device(y.device):
+            rc = N.lib().mtts_mel_from_wav(N.ptr(y), int(y.dtype == torch.int16), N.ptr(lengths), N.ptr(basis),
+                                           N.ptr(lo), N.ptr(hi), N.ptr(tw), N.ptr(win), B, L, self.n_fft,
+                                           self.win_size, self.hop_size, self.num_mels, 1e-5, float(mel_mean),
+                                           float(mel_std), 0.0, N.ptr(out), N.ptr(mel_lengths),
+                                           N.stream_handle(y.device))
+        N.check(rc, "mtts_mel_from_wav")
+        return out, mel_lengths.to(torch.int64)
+
+
+class MelStatistics:
+    """The ``data_statistics`` of a dataset from its mel batches: ``update(mel, mel_lengths)`` adds the float64 sums
+    of the valid frames (one launch of mtts_mel_stats, accumulators stay on the device, no synchronisation);
+    ``result()`` returns ``{"mel_mean", "mel_std"}`` for ``MatchaTTS(data_statistics=...)`` and for the ``mel_mean`` /
+    ``mel_std`` of ``MelSpectrogram.batch``.  mean = sum v / n, std = sqrt(sum v^2 / n - mean^2) with n = num_mels *
+    sum mel_lengths: the population form of upstream Matcha's data-statistics script."""
+
+    def __init__(self):
+        self._sums = None  # float64 [2] on the device: sum v, sum v^2
+        self._frames = None  # int64 [] on the device
+        self._num_mels = None
+
+    def update(self, mel, mel_lengths):
+        if mel.dim() != 3 or mel.dtype != torch.float32:
+            raise ValueError(f"MelStatistics.update expects mel float32 [B, num_mels, F], got {mel.dtype} "
+                             f"{tuple(mel.shape)}")
+        N.require_device(mel)
+        B, n_mels, F = mel.shape
+        if self._num_mels not in (None, n_mels):
+            raise ValueError(f"num_mels changed between updates: {self._num_mels} then {n_mels}")
+        ml = torch.as_tensor(mel_lengths).reshape(-1)
+        if ml.is_floating_point() or ml.numel() != B:
+            raise ValueError(f"mel_lengths must be {B} integers, got {ml.dtype} x {ml.numel()}")
+        ml = ml.to(device=mel.device, dtype=torch.int32).clamp(0, F).contiguous()
+        mel = mel.detach().contiguous()
+        stats = torch.empty((B, 2), dtype=torch.float64, device=mel.device)
+        with torch.cuda.device(mel.device):
+            rc = N.lib().mtts_mel_stats(N.ptr(mel), N.ptr(ml), B, n_mels, F, N.ptr(stats), N.stream_handle(mel.device))
+        N.check(rc, "mtts_mel_stats")
+        sums, frames = stats.sum(0), ml.sum(dtype=torch.int64)
+        self._sums = sums if self._sums is None else self._sums + sums
+        self._frames = frames if self._frames is None else self._frames + frames
+        self._num_mels = n_mels
+        return self
+
+    def state(self):
+        """(float64 [2]: sum v and sum v^2, int64 []: frames added) on the device, without synchronising; None before
+        the first update."""
+        return None if self._sums is None else (self._sums, self._frames)
+
+    @staticmethod
+    def from_sums(total, total_sq, count):
+        """{"mel_mean", "mel_std"} from sum v, sum v^2 and the number of values."""
+        if count <= 0:
+            raise ValueError("MelStatistics: no frames were added")
+        mean = float(total) / count
+        return {"mel_mean": mean, "mel_std": math.sqrt(max(float(total_sq) / count - mean * mean, 0.0))}
+
+    def result(self):
+        if self._sums is None:
+            raise ValueError("MelStatistics: no frames were added")
+        total, total_sq = self._sums.tolist()
+        return self.from_sums(total, total_sq, self._num_mels * int(self._frames))
+
 
 # ---- mel -> waveform without a vocoder checkpoint (reference: generate.py:66-113) ----------------------------------
 GL_NFFT, GL_HOP = 1024, 256  # include/mtts_griffinlim.h: the one STFT geometry the kernels serve
+MEL_MIN_SAMPLES = (GL_NFFT - GL_HOP) // 2 + 1  # MelSpectrogram.batch: the shortest utterance a reflect pad by 384 accepts
 
 _gl_tables: dict = {}
 
