@@ -14,7 +14,14 @@ Every operator is a torch.autograd.Function whose forward AND backward run in li
   layer_norm_tm                                    -> mtts_layernorm_fwd / _bwd
   attention_tm                                     -> mtts_attention_fwd / _bwd (flash attention)
 GEMM precision follows the caller: inside a bf16 torch.autocast region the GEMMs use bf16 MFMA with
-fp32 accumulation, otherwise exact-fp32 MFMA (the parity mode).  Activations stay fp32 in HBM.
+fp32 accumulation, otherwise exact-fp32 MFMA (32-true).  Which operands a bf16 region's FORWARD GEMMs take
+(one bf16 weight plane, split planes, bf16x3 / bf16x6, fp32) is the forward-precision policy: it lives in
+_policy.py, is read here through its named predicates only, and only in a forward -- an op's backward uses
+the `prec` its forward captured and one-plane dgrad operands.  set_weight_split, precise_forward,
+parity_policy and the encoder_precision_* readers are re-exported here for their callers.
+The residual stream stays fp32 in HBM; in a bf16 region an activation that is only ever an MFMA operand is
+stored bf16 (LayerNorm outputs except under precise_forward, q|k|v / o and their gradients, the FeedForward's
+hidden rows, pre-activation and its gradient, GroupNorm+Mish outputs where asked with out_bf16).
 Dropout (train mode) is a counter-based mask generated in the GEMM epilogues and regenerated in the
 backward, so no mask tensor is stored.
 """
@@ -24,16 +31,31 @@ import contextlib
 import contextvars
 import ctypes
 import functools
-import os
 import math
 
 import torch
 import torch.nn.functional as F
 
 from matcha import _native as N
+from matcha.models.components import _policy
 from matcha.models.components._defer import _grad_sums, _keep_partials, keep_for_side, param_grad_side_stream
+from matcha.models.components._policy import FF1_SPLIT as _FF1_SPLIT  # MTTS_PARITY_FF1_SPLIT
+from matcha.models.components._policy import (PACK_BF16_SPLIT, PACK_BF16_SPLIT3, PREC_BF16, PREC_FP32,  # noqa: F401
+                                              parity_policy, precise_forward, set_weight_split)
 
-PREC_FP32, PREC_BF16 = 0, 1
+
+def weight_split_enabled() -> bool:
+    return _policy.policy().weight_split
+
+
+def encoder_precision_for_parity() -> str:
+    return _policy.PARITY_ENCODER
+
+
+def encoder_precision_default() -> str:
+    return _policy.policy().encoder
+
+
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_RELU, ACT_DRELU = 0, 1, 2, 3, 4
 
 KERNELS: dict[str, str] = {
@@ -56,101 +78,7 @@ GEMM_F_FAST_ACT = 0x8  # MTTS_GEMM_F_FAST_ACT: 1.5e-7-accurate erf in GELU epilo
 GEMM_F_PRE_BF16 = 0x10  # MTTS_GEMM_F_PRE_BF16: C_pre written / aux read as bf16
 WGRAD_F_DY_BF16 = 0x20  # MTTS_WGRAD_F_DY_BF16: the weight gradient's dY holds bf16
 GEMM_F_W_SPLIT = 0x40  # MTTS_GEMM_F_W_SPLIT: W holds a hi and a lo bf16 plane (two MFMAs per product)
-# Weight planes of the bf16-mixed forward GEMMs.  Split (two bf16 planes, hi + rounding residual): the
-# rounding of the fp32 weights is a static model perturbation and is the bf16 loss error
-# (tools/r3/precision_budget.py, last runnable at 3dd8270: prior 2.9e-4 / diff 2.1e-4 from weight rounding
-# alone, activations 3.8e-5 / 2.1e-5 at B=32) -- with split planes bf16-mixed meets the 1e-4 loss bar at the
-# bench batch, at ~+50 % forward-GEMM time (bench.py reports both lines).  Default one plane (the throughput
-# mode); set_weight_split(True) selects the split planes.
-_W_SPLIT = False
-
-
 GEMM_F_A_SPLIT = 0x80  # MTTS_GEMM_F_A_SPLIT: with W_SPLIT, fp32 A split into hi + lo planes (bf16x3)
-# precise_forward(): inside a bf16-mixed region, the forward GEMMs take split weight planes AND split A
-# operands (A_hi W_hi + A_hi W_lo + A_lo W_hi: ~16 significant bits per operand, fp32 accumulate) and the
-# attention forward runs exact fp32 MFMA; the backward of the same ops stays bf16 one-plane.  The
-# text encoder runs this way in the parity policy (MatchaTTS.encoder_precision = "bf16x3"): its
-# activations' bf16 rounding decides the alignment's near-ties (tools/r3/precision_budget.py, last
-# runnable at 3dd8270).
-_PRECISE: contextvars.ContextVar = contextvars.ContextVar("mtts_precise_fwd", default=False)
-
-
-@contextlib.contextmanager
-def precise_forward(on: bool | str = True):
-    """on: True / "bf16x3" (split bf16 operands, three MFMAs per product), "bf16x6" (three exact planes per
-    operand, six MFMAs per product: fp32-faithful, MTTS_GEMM_F_SPLIT3) or "fp32" (the forward GEMMs on the
-    exact-fp32 MFMA with fp32 packed weights -- the 32-true arithmetic, so the forward's outputs are those of
-    32-true; round 4: bf16x3 left one alignment near-tie of the B=4 reference fixture flipped); False: off.
-    The backward of the same ops stays bf16 one-plane either way."""
-    tok = _PRECISE.set(("bf16x3" if on is True else on) if on else False)
-    try:
-        yield
-    finally:
-        _PRECISE.reset(tok)
-
-
-def _fwd_fp32() -> bool:
-    """precise_forward("fp32") is active: bf16-region forward GEMMs run as exact fp32."""
-    return _PRECISE.get() == "fp32"
-
-
-def set_weight_split(on: bool) -> bool:
-    """Selects one (False) or two (True) bf16 weight planes for the bf16-mixed forward GEMMs from the next
-    forward on; returns the previous setting.  (Captured graphs keep the packing they were captured with.)"""
-    global _W_SPLIT
-    old, _W_SPLIT = _W_SPLIT, bool(on)
-    return old
-
-
-_WSPLIT_CV: contextvars.ContextVar = contextvars.ContextVar("mtts_w_split", default=None)
-# the text encoder's precision inside bf16-mixed when the model does not set its own
-# (MatchaTTS.encoder_precision): "bf16", "bf16x3" / "bf16x6" / "fp32fwd" (precise_forward) or "fp32"
-_ENC_PREC: contextvars.ContextVar = contextvars.ContextVar("mtts_encoder_precision", default="bf16")
-
-
-def weight_split_enabled() -> bool:
-    v = _WSPLIT_CV.get()
-    return _W_SPLIT if v is None else v
-
-
-# The decoder FeedForward's GELU up-projection keeps ONE bf16 weight plane under the parity policy: its share of the
-# diffusion loss's weight-rounding error is ~3.5 % (tools/r3/weight_sensitivity.py), and its split planes cost the
-# most of any GEMM (the GELU epilogue pins it to the register schedule).  Measured (profiles/r04/ff1_one_plane/):
-# step 7.99 / 8.01 -> 7.85 / 7.86 ms; parity errors (prior, diff) B=4 vs the reference fixture 0 / 1.2e-5, B=32
-# 0 / 3.4e-7, 512 x 4096 1.9e-7 / 3.3e-5, alignment exact in all three.  MTTS_PARITY_FF1_SPLIT=1: split it too.
-# The down-projection (~3 % share) is always split under the policy (A/B last runnable at 3dd8270).
-_FF1_SPLIT = os.environ.get("MTTS_PARITY_FF1_SPLIT", "0") != "0"
-
-# the parity policy's text-encoder forward: "fp32fwd" (exact-fp32 MFMA: 32-true's arithmetic) or "bf16x6"
-# (three exact bf16 planes per operand, six MFMAs).  bf16x6 measured 8.16 vs 8.05 ms per step and 1-3x the
-# fp32 kernel's error, enough to move 2 of 437 durations at B=4 (profiles/r04/x6): fp32fwd stays the
-# default; MTTS_PARITY_ENCODER selects
-_PARITY_ENC = os.environ.get("MTTS_PARITY_ENCODER", "fp32fwd")
-
-
-def encoder_precision_for_parity() -> str:
-    return _PARITY_ENC
-
-
-@contextlib.contextmanager
-def parity_policy(on: bool = True):
-    """bf16-parity inside a bf16 autocast region (the Trainer's "bf16-parity" precision): split weight
-    planes for every forward GEMM but the decoder FeedForward's GELU up-projection (_FF1_SPLIT) and the text
-    encoder's forward on the exact-fp32 MFMA
-    (precise_forward("fp32"); its backward stays bf16)."""
-    t1 = _WSPLIT_CV.set(True if on else None)
-    t2 = _ENC_PREC.set(_PARITY_ENC if on else "bf16")
-    try:
-        yield
-    finally:
-        _ENC_PREC.reset(t2)
-        _WSPLIT_CV.reset(t1)
-
-
-def encoder_precision_default() -> str:
-    return _ENC_PREC.get()
-PACK_BF16_SPLIT = 2  # pack-cache kind: the bf16 hi + lo planes of a forward operand
-PACK_BF16_SPLIT3 = 3  # pack-cache kind: hi + mid + lo bf16 planes (== w exactly) of a bf16x6 forward operand
 GEMM_F_SPLIT3 = 0x100  # MTTS_GEMM_F_SPLIT3: three weight planes, fp32 A split in the kernel (bf16x6)
 PACK_THREE_PLANES = 1 << 62  # MTTS_PACK_THREE_PLANES (mtts_pack_job.lo_off flag)
 
@@ -419,20 +347,8 @@ def _run_pack(specs, prec, stream=None, alloc=None):
 
 
 def _pack_kind(spec: PackSpec, prec: int) -> int:
-    """bf16 forward operands: fp32 under precise_forward("fp32"), the split planes when selected
-    (set_weight_split, precise_forward("bf16x3")); everything else as prec."""
-    if prec == PREC_BF16 and not spec.dgrad:
-        # one_plane is the parity POLICY's choice (parity_policy()); set_weight_split(True) alone splits
-        # every forward operand, so its error numbers mean what the mode says (ADVICE r4)
-        if spec.one_plane and not _PRECISE.get() and _WSPLIT_CV.get() is not None:
-            return prec
-        if _fwd_fp32():
-            return PREC_FP32
-        if _PRECISE.get() == "bf16x6":
-            return PACK_BF16_SPLIT3
-        if weight_split_enabled() or _PRECISE.get():
-            return PACK_BF16_SPLIT
-    return prec
+    """The pack-cache kind of `spec` in a `prec` region under the forward-precision policy."""
+    return _policy.policy().operand_kind(spec, prec)
 
 
 _PACK_SCOPE: contextvars.ContextVar = contextvars.ContextVar("mtts_pack_scope", default=None)
@@ -582,7 +498,7 @@ def _gemm(A, Ti, To, nb, in_stride, offs, cin, Wp, Kp, N_, C, To_full, out_strid
         if A.dtype != torch.float32:
             A = A.float()
     # bf16x3 (precise_forward): the split weights' GEMM also splits its fp32 A operand -- register schedules
-    a_split = w_split and _PRECISE.get() and A.dtype == torch.float32
+    a_split = _policy.policy().split_a(w_split, A.dtype)
     if a_split:
         tile_cfg, splits = (tile_cfg if 0 <= tile_cfg < GEMM_GLDS else -1), 1
     if w_split and Wp.shape[0] != 2 * N_:
@@ -1388,7 +1304,7 @@ class _AttentionTM(torch.autograd.Function):
         lse = torch.empty(B, heads, T, device=qkv.device, dtype=torch.float32)
         seed = _new_seed(qkv.device) if dropout_p > 0 else None
         # precise_forward: exact-fp32 MFMA forward (fp32 q|k|v here), the backward in the region's bf16
-        _attn_fwd(qkv, bias, o, lse, heads, PREC_FP32 if _PRECISE.get() else prec, dropout_p, seed)
+        _attn_fwd(qkv, bias, o, lse, heads, _policy.policy().attention_prec(prec), dropout_p, seed)
         ctx.save_for_backward(qkv, bias, o, lse)
         ctx.heads, ctx.prec, ctx.drop = heads, prec, (dropout_p, seed)
         return o
@@ -1502,7 +1418,7 @@ class _PreLNAttentionTM(torch.autograd.Function):
         lnw, lnb = _f32c(ln_w), _f32c(ln_b)
         # bf16-mixed: the LN output is only the q|k|v projection's A operand -- stored bf16 (A/B last runnable at
         # 3dd8270; not under precise_forward: its bf16x3 / fp32 GEMMs read the fp32 A's low bits -- ADVICE r5)
-        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, prec == PREC_BF16 and not _PRECISE.get())
+        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, _policy.policy().ln_out_bf16(prec))
         Wqkv, Kq = packed(spec_linear((wq, wk, wv)), prec)
         Wo, Ko = packed(spec_linear((w_out,)), prec)
         ctx.wqkv_t = packed(spec_linear((wq, wk, wv), dgrad=True), prec)
@@ -1582,7 +1498,7 @@ class _PreLNFeedForwardTM(torch.autograd.Function):
         # the weight-stationary kernel, which rounds an fp32 A to bf16 at its fragment read anyway -- the same
         # products, half the bytes, and dW1 reads it too
         # (not under precise_forward, whose split-A GEMMs need the fp32 LN output -- ADVICE r5)
-        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, prec == PREC_BF16 and not _PRECISE.get())
+        n, mean, rstd = _ln_fwd(h2, lnw, lnb, eps, _policy.policy().ln_out_bf16(prec))
         y, z, hid, seed, ctx.w1t, ctx.w2t = _ff_fwd(n, w1, b1, w2, b2, h2, dropout_p, prec,
                                                     (not _FF1_SPLIT, False), (True, True))
         ctx.save_for_backward(h2, lnw, lnb, mean, rstd, n, z, hid)

@@ -21,6 +21,7 @@ import matcha.utils.monotonic_align as monotonic_align
 from matcha.models.baselightningmodule import BaseLightningClass
 from matcha.models.components import _defer as D
 from matcha.models.components import _ops as O
+from matcha.models.components import _policy
 from matcha.models.components.flow_matching import ConditionalFlowMatching as CFM
 from matcha.models.components.text_encoder import TextEncoder
 from matcha.utils.model import denormalize, fix_len_compatibility, generate_path, sequence_mask
@@ -29,21 +30,13 @@ from matcha.utils.model import denormalize, fix_len_compatibility, generate_path
 _PREFETCH = os.environ.get("MTTS_PREFETCH", "1") != "0"
 
 
-class _nullctx:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
-
-
 class MatchaTTS(BaseLightningClass):
     # text encoder precision inside a bf16-mixed region (see forward): "bf16" (autocast's), "fp32fwd" (the
     # forward on the exact-fp32 MFMA with fp32 weights -- 32-true's forward arithmetic --, backward bf16: the
     # parity policy since round 4), "bf16x3" (forward GEMMs as split bf16 operands A_hi W_hi + A_hi W_lo +
     # A_lo W_hi and an fp32 attention forward, backward bf16: ~16 significant bits, left an alignment
     # near-tie flipped), "fp32" (exact fp32 MFMA forward and backward)
-    # None: the ambient default (_ops.parity_policy sets "fp32fwd", otherwise "bf16")
+    # None: the ambient default (_policy.parity_policy sets MTTS_PARITY_ENCODER's "fp32fwd", otherwise "bf16")
     encoder_precision = None
     last_seg = None  # forward(out_size=...) on the device: the windows of the last forward (see forward)
 
@@ -130,16 +123,7 @@ class MatchaTTS(BaseLightningClass):
 
     def _encoder_ctx(self, device_type):
         """The text encoder's precision policy (encoder_precision, see forward) as a context manager."""
-        enc_prec = self.encoder_precision or O.encoder_precision_default()
-        if enc_prec == "fp32":
-            return torch.autocast(device_type=device_type, enabled=False)
-        if enc_prec == "bf16x3":
-            return O.precise_forward("bf16x3")
-        if enc_prec == "fp32fwd":
-            return O.precise_forward("fp32")
-        if enc_prec == "bf16x6":
-            return O.precise_forward("bf16x6")
-        return _nullctx()
+        return _policy.encoder_context(self.encoder_precision or _policy.policy().encoder, device_type)
 
     @torch.no_grad()
     def align(self, x, x_lengths, y, y_lengths):

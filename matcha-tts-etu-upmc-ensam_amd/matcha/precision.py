@@ -27,16 +27,16 @@ import contextlib
 import torch
 
 from matcha.models.components import _ops as O
+from matcha.models.components._policy import TRAINER_PRECISIONS, trainer_precision
 
-PRECISIONS = ("32-true", "bf16-mixed", "bf16-parity")
+PRECISIONS = tuple(TRAINER_PRECISIONS)
 
 
 @contextlib.contextmanager
 def precision_context(precision: str, model=None):
-    """The Trainer's numerics for `precision` (Trainer._autocast): bf16 autocast for the bf16 modes, plus
-    _ops.parity_policy() (split weight planes but the decoder FF up-projection, the text encoder's forward on
-    the exact-fp32 MFMA) for bf16-parity.  `model.encoder_precision` is cleared to the ambient default for the
-    duration (restored after)."""
+    """The Trainer's numerics for `precision` (_policy.trainer_precision, what Trainer._autocast enters) with
+    nothing else in force: the process-wide weight split is off and `model.encoder_precision` cleared to the
+    ambient default for the duration (both restored after)."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision {precision!r} not in {PRECISIONS}")
     old_enc = getattr(model, "encoder_precision", None) if model is not None else None
@@ -44,11 +44,7 @@ def precision_context(precision: str, model=None):
         model.encoder_precision = None
     old_split = O.set_weight_split(False)
     try:
-        with contextlib.ExitStack() as st:
-            if precision != "32-true":
-                st.enter_context(torch.autocast("cuda", dtype=torch.bfloat16))
-            if precision == "bf16-parity":
-                st.enter_context(O.parity_policy())
+        with trainer_precision(precision):
             yield
     finally:
         O.set_weight_split(old_split)

@@ -57,6 +57,7 @@ import torch.distributed as dist
 from matcha import _native as N
 from matcha.models.components import _ops as OPS
 from matcha.models.components._defer import deferred_grad_sums
+from matcha.models.components._policy import trainer_precision
 from matcha.models.matcha_tts import MatchaTTS
 
 
@@ -195,7 +196,7 @@ class TrainConfig:
     # "32-true" (reference), "bf16-mixed" (autocast), or "bf16-parity": bf16-mixed with split bf16 weight
     # planes (every forward GEMM but the decoder FF's GELU up-projection) and the text encoder's forward on the
     # exact-fp32 MFMA -- alignment exact, losses within 1e-4 of 32-true
-    # (tests/test_headline_gpu.py; _ops.parity_policy)
+    # (tests/test_headline_gpu.py; components/_policy.py)
     precision: str = "32-true"
     graph: bool = False
     lr: float = 1e-4
@@ -294,13 +295,7 @@ class Trainer:
 
     # ------------------------------------------------------------------------------------ common
     def _autocast(self):
-        if self.cfg.precision in ("bf16-mixed", "bf16-parity") and self.dev.type == "cuda":
-            st = contextlib.ExitStack()
-            st.enter_context(torch.autocast(device_type="cuda", dtype=torch.bfloat16))
-            if self.cfg.precision == "bf16-parity":
-                st.enter_context(OPS.parity_policy())
-            return st
-        return contextlib.nullcontext()
+        return trainer_precision(self.cfg.precision) if self.dev.type == "cuda" else contextlib.nullcontext()
 
     def _fwd_bwd(self, batches, sync_ctx=None):
         n = len(batches)

@@ -41,10 +41,12 @@ FP32_LOSS_RTOL = 1e-4       # north star: mel / flow-matching loss within 1e-4 r
 PARITY_RTOL = np.array([1e-4, 1e-4, 1e-4])    # bf16-parity (dur, prior, diff): every loss at the bar
 BF16_LOSS_RTOL = np.array([0.15, 5e-4, 5e-4])  # bf16-mixed, one weight plane: measured, misses the bar
 BF16_ATTN_AGREE = 0.99      # one plane: fraction of [Tx, Ty] alignment cells equal to the fp32 reference path
-# precision -> (bf16 autocast, split weight planes, MatchaTTS.encoder_precision)
-MODES = {"32-true": (False, False, "bf16"), "bf16-mixed": (True, False, "bf16"),
-         "bf16-parity": (True, True, "fp32fwd"), "bf16-parity-fp32enc": (True, True, "fp32"),
-         "bf16-parity-bf16x3": (True, True, "bf16x3"), "bf16-parity-bf16x6": (True, True, "bf16x6")}
+# the Trainer's precisions run under its own contexts (matcha.precision.precision_context); the extra modes on the
+# PROCESS-WIDE split, not the parity policy: mode -> (bf16 autocast, split weight planes, MatchaTTS.encoder_precision)
+TRAINER_MODES = ("32-true", "bf16-mixed", "bf16-parity")
+EXTRA_MODES = {"bf16-parity-fp32enc": (True, True, "fp32"), "bf16-parity-bf16x3": (True, True, "bf16x3"),
+               "bf16-parity-bf16x6": (True, True, "bf16x6")}
+MODES = TRAINER_MODES + tuple(EXTRA_MODES)
 # bf16x6 is not at the bar: measured B=4 alignment 0.99990 (2 of 437 durations moved), duration loss 4e-4
 PARITY_MODES = ("bf16-parity", "bf16-parity-fp32enc")
 # The at-bar modes' BACKWARD is bf16: their gradients pinned against the reference fixture's
@@ -70,10 +72,10 @@ def run_precision(model, precision, fn):
     from matcha.models.components import _ops as O
     from matcha.precision import precision_context
 
-    if precision in ("32-true", "bf16-mixed", "bf16-parity"):  # the Trainer's own precisions, its contexts
+    if precision in TRAINER_MODES:  # the Trainer's own precisions, its contexts
         with precision_context(precision, model):
             return fn()
-    amp, split, enc = MODES[precision]
+    amp, split, enc = EXTRA_MODES[precision]
     old = O.set_weight_split(split)
     model.encoder_precision = enc
     try:
