@@ -9,19 +9,9 @@ import ctypes
 import torch
 
 from matcha import _native as N
-
-ACC_NONE, ACC_INIT, ACC_ADD, ACC_MEAN = 0, 1, 2, 3
-MAX_TAPS = 11
-ERR_INVALID_ARG, ERR_SHAPE = -1, -2
-
-
-class VocConvArgs(ctypes.Structure):
-    """mtts_voc_conv_args"""
-    _fields_ = [("A", ctypes.c_void_p), ("W", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("residual", ctypes.c_void_p), ("C", ctypes.c_void_p), ("acc", ctypes.c_void_p),
-                ("B", ctypes.c_int32), ("L", ctypes.c_int32), ("cin", ctypes.c_int32), ("N", ctypes.c_int32),
-                ("k", ctypes.c_int32), ("d", ctypes.c_int32), ("leaky", ctypes.c_int32), ("slope", ctypes.c_float),
-                ("acc_mode", ctypes.c_int32), ("acc_div", ctypes.c_float)]
+from matcha._abi import (MTTS_ERR_INVALID_ARG as ERR_INVALID_ARG, MTTS_ERR_SHAPE as ERR_SHAPE,  # noqa: F401
+                         MTTS_VOC_ACC_ADD as ACC_ADD, MTTS_VOC_ACC_INIT as ACC_INIT, MTTS_VOC_ACC_MEAN as ACC_MEAN,
+                         MTTS_VOC_ACC_NONE as ACC_NONE, MTTS_VOC_MAX_TAPS as MAX_TAPS, VocConvArgs)
 
 
 def pack_conv(w: torch.Tensor) -> torch.Tensor:

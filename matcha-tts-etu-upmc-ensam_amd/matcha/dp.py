@@ -45,16 +45,6 @@ import torch.distributed as dist
 
 from matcha import _native as N
 
-N.register("mtts_dp_unique_id", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t])
-N.register("mtts_dp_comm_init", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.POINTER(ctypes.c_void_p)])
-N.register("mtts_dp_allreduce_f32", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                   ctypes.c_void_p])
-N.register("mtts_dp_comm_query", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
-                                                ctypes.POINTER(ctypes.c_int32)])
-N.register("mtts_dp_comm_destroy", ctypes.c_int, [ctypes.c_void_p])
-N.register("mtts_dp_rccl_version", ctypes.c_int, [])
-
 
 class TorchComm:
     """torch.distributed all-reduce (sum, then / world): eager only."""

@@ -37,6 +37,19 @@ import torch
 import torch.nn.functional as F
 
 from matcha import _native as N
+# the C ABI's structs and constants under the names this module's callers use (matcha/_abi.py holds the values)
+from matcha._abi import AttnArgs, AttnGrads, ConvGemmArgs, ConvWgradArgs, PackJob  # noqa: F401
+from matcha._abi import (MTTS_ACT_NONE as ACT_NONE, MTTS_ACT_GELU as ACT_GELU, MTTS_ACT_DGELU as ACT_DGELU,
+                         MTTS_ACT_RELU as ACT_RELU, MTTS_ACT_DRELU as ACT_DRELU, MTTS_GEMM_GLDS as GEMM_GLDS,
+                         MTTS_GEMM_F_BINARY_SCALE as GEMM_F_BINARY_SCALE, MTTS_GEMM_F_A_BF16 as GEMM_F_A_BF16,
+                         MTTS_GEMM_F_C_BF16 as GEMM_F_C_BF16, MTTS_GEMM_F_FAST_ACT as GEMM_F_FAST_ACT,
+                         MTTS_GEMM_F_PRE_BF16 as GEMM_F_PRE_BF16, MTTS_GEMM_F_W_SPLIT as GEMM_F_W_SPLIT,
+                         MTTS_GEMM_F_A_SPLIT as GEMM_F_A_SPLIT, MTTS_GEMM_F_SPLIT3 as GEMM_F_SPLIT3,
+                         MTTS_WGRAD_F_DY_BF16 as WGRAD_F_DY_BF16, MTTS_NORM_F_Y_BF16 as NORM_F_Y_BF16,
+                         MTTS_NORM_F_X_BF16 as NORM_F_X_BF16, MTTS_NORM_F_DY_BF16 as NORM_F_DY_BF16,
+                         MTTS_PACK_THREE_PLANES as PACK_THREE_PLANES, MTTS_ATTN_F_IO_BF16 as ATTN_F_IO_BF16,
+                         MTTS_ROWS_MAX_MATS as ROWS_MAX_MATS, MTTS_ROWS_ACT_NONE as ROWS_ACT_NONE,
+                         MTTS_ROWS_ACT_SILU as ROWS_ACT_SILU, MTTS_ROWS_ACT_MISH as ROWS_ACT_MISH)
 from matcha.models.components import _policy
 from matcha.models.components._defer import _grad_sums, _keep_partials, keep_for_side, param_grad_side_stream
 from matcha.models.components._policy import FF1_SPLIT as _FF1_SPLIT  # MTTS_PARITY_FF1_SPLIT
@@ -56,8 +69,6 @@ def encoder_precision_default() -> str:
     return _policy.policy().encoder
 
 
-ACT_NONE, ACT_GELU, ACT_DGELU, ACT_RELU, ACT_DRELU = 0, 1, 2, 3, 4
-
 KERNELS: dict[str, str] = {
     "conv_tm": "mtts_conv_gemm/mtts_conv_wgrad",
     "conv_transpose_tm": "mtts_conv_gemm/mtts_conv_wgrad",
@@ -69,105 +80,6 @@ KERNELS: dict[str, str] = {
     "rope_tm": "mtts_rope_qk",
     "attention_tm": "mtts_attention_fwd/mtts_attention_bwd",
 }
-
-
-GEMM_F_BINARY_SCALE = 0x1  # include/mtts_decoder.h MTTS_GEMM_F_BINARY_SCALE
-GEMM_F_A_BF16 = 0x2  # MTTS_GEMM_F_A_BF16: A operand stored bf16 (bf16-mixed activations)
-GEMM_F_C_BF16 = 0x4  # MTTS_GEMM_F_C_BF16: output stored bf16
-GEMM_F_FAST_ACT = 0x8  # MTTS_GEMM_F_FAST_ACT: 1.5e-7-accurate erf in GELU epilogues (bf16-mixed only)
-GEMM_F_PRE_BF16 = 0x10  # MTTS_GEMM_F_PRE_BF16: C_pre written / aux read as bf16
-WGRAD_F_DY_BF16 = 0x20  # MTTS_WGRAD_F_DY_BF16: the weight gradient's dY holds bf16
-GEMM_F_W_SPLIT = 0x40  # MTTS_GEMM_F_W_SPLIT: W holds a hi and a lo bf16 plane (two MFMAs per product)
-GEMM_F_A_SPLIT = 0x80  # MTTS_GEMM_F_A_SPLIT: with W_SPLIT, fp32 A split into hi + lo planes (bf16x3)
-GEMM_F_SPLIT3 = 0x100  # MTTS_GEMM_F_SPLIT3: three weight planes, fp32 A split in the kernel (bf16x6)
-PACK_THREE_PLANES = 1 << 62  # MTTS_PACK_THREE_PLANES (mtts_pack_job.lo_off flag)
-
-GEMM_GLDS = 32  # MTTS_GEMM_GLDS: first LDS-DMA schedule id
-
-
-class ConvGemmArgs(ctypes.Structure):
-    _fields_ = [("A", ctypes.c_void_p), ("a_scale", ctypes.c_void_p), ("lda", ctypes.c_int32),
-                ("Ti", ctypes.c_int32), ("To", ctypes.c_int32), ("nb", ctypes.c_int32),
-                ("in_stride", ctypes.c_int32), ("ntaps", ctypes.c_int32), ("off", ctypes.c_int32 * 8),
-                ("cin", ctypes.c_int32), ("W", ctypes.c_void_p), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
-                ("Kp", ctypes.c_int32), ("bias", ctypes.c_void_p), ("act", ctypes.c_int32),
-                ("residual", ctypes.c_void_p), ("ldr", ctypes.c_int32), ("c_scale", ctypes.c_void_p),
-                ("C", ctypes.c_void_p), ("ldc", ctypes.c_int32), ("To_full", ctypes.c_int32),
-                ("out_stride", ctypes.c_int32), ("out_off", ctypes.c_int32), ("C_pre", ctypes.c_void_p),
-                ("aux", ctypes.c_void_p), ("ldaux", ctypes.c_int32), ("dropout_p", ctypes.c_float),
-                ("seed", ctypes.c_void_p), ("flags", ctypes.c_int32)]
-
-
-class ConvWgradArgs(ctypes.Structure):
-    _fields_ = [("dY", ctypes.c_void_p), ("ldy", ctypes.c_int32), ("To_full", ctypes.c_int32),
-                ("out_stride", ctypes.c_int32), ("out_off", ctypes.c_int32), ("A", ctypes.c_void_p),
-                ("a_scale", ctypes.c_void_p), ("lda", ctypes.c_int32), ("Ti", ctypes.c_int32),
-                ("To", ctypes.c_int32), ("nb", ctypes.c_int32), ("in_stride", ctypes.c_int32),
-                ("ntaps", ctypes.c_int32), ("off", ctypes.c_int32 * 8), ("cin", ctypes.c_int32),
-                ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("flags", ctypes.c_int32)]
-
-
-class AttnArgs(ctypes.Structure):
-    _fields_ = [("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("ldq", ctypes.c_int32),
-                ("key_bias", ctypes.c_void_p), ("o", ctypes.c_void_p), ("ldo", ctypes.c_int32),
-                ("lse", ctypes.c_void_p), ("B", ctypes.c_int32), ("T", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("D", ctypes.c_int32), ("scale", ctypes.c_float), ("dropout_p", ctypes.c_float),
-                ("seed", ctypes.c_void_p), ("flags", ctypes.c_int32)]
-ATTN_F_IO_BF16 = 0x1  # include/mtts_decoder.h MTTS_ATTN_F_IO_BF16
-
-
-class AttnGrads(ctypes.Structure):
-    _fields_ = [("dout", ctypes.c_void_p), ("lddo", ctypes.c_int32), ("dq", ctypes.c_void_p),
-                ("dk", ctypes.c_void_p), ("dv", ctypes.c_void_p), ("ldd", ctypes.c_int32)]
-
-
-class PackJob(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", ctypes.c_int32), ("C", ctypes.c_int32),
-                ("ntaps", ctypes.c_int32), ("Kp", ctypes.c_int32), ("ld", ctypes.c_int32), ("sr", ctypes.c_int64),
-                ("sc", ctypes.c_int64), ("sj", ctypes.c_int64), ("j0", ctypes.c_int32), ("js", ctypes.c_int32),
-                ("lo_off", ctypes.c_int64)]
-
-
-_P, _I, _F, _SZ, _U = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint32
-_I64 = ctypes.c_int64
-N.register("mtts_conv_gemm", ctypes.c_int, [ctypes.POINTER(ConvGemmArgs), _I, _P])
-N.register("mtts_conv_gemm_tile", ctypes.c_int, [ctypes.POINTER(ConvGemmArgs), _I, _I, _P])
-N.register("mtts_conv_gemm_workspace_size", _SZ, [ctypes.POINTER(ConvGemmArgs), _I, _I, _I])
-N.register("mtts_conv_gemm_ws", ctypes.c_int, [ctypes.POINTER(ConvGemmArgs), _I, _I, _I, _P, _SZ, _P])
-N.register("mtts_conv_wgrad_workspace_size", _SZ, [ctypes.POINTER(ConvWgradArgs)])
-N.register("mtts_conv_wgrad", ctypes.c_int,
-           [ctypes.POINTER(ConvWgradArgs), _I, _P, _I64, _I64, _I64, _P, _I, _P, _SZ, _P])
-N.register("mtts_conv_wgrad_tile", ctypes.c_int,
-           [ctypes.POINTER(ConvWgradArgs), _I, _I, _I, _I, _P, _I64, _I64, _I64, _P, _I, _P, _SZ, _P])
-N.register("mtts_gn_mish_fwd", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P])
-N.register("mtts_gn_mish_bwd_workspace_size", _SZ, [_I, _I])
-N.register("mtts_gn_mish_bwd", ctypes.c_int,
-           [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P])
-N.register("mtts_gn_mish_fwd_ex", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P])
-N.register("mtts_gn_mish_bwd_ex", ctypes.c_int,
-           [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P])
-NORM_F_X_BF16, NORM_F_DY_BF16 = 0x200, 0x400  # include/mtts_decoder.h
-N.register("mtts_layernorm_fwd", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _F, _P, _P])
-N.register("mtts_layernorm_bwd_workspace_size", _SZ, [_I, _I])
-N.register("mtts_layernorm_bwd", ctypes.c_int,
-           [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _SZ, _P])
-N.register("mtts_dropout_apply", ctypes.c_int, [_P, _P, _I, _I, _I, _F, _P, _P])
-N.register("mtts_act_dropout_bwd", ctypes.c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P])
-N.register("mtts_act_dropout_bwd_scaled", ctypes.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P])
-N.register("mtts_rope_qk", ctypes.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P])
-N.register("mtts_pack_weights", ctypes.c_int, [ctypes.POINTER(PackJob), _I, _I, _P])
-N.register("mtts_attention_fwd", ctypes.c_int, [ctypes.POINTER(AttnArgs), _I, _P])
-N.register("mtts_attention_bwd_workspace_size", _SZ, [_I, _I, _I])
-N.register("mtts_attention_bwd", ctypes.c_int, [ctypes.POINTER(AttnArgs), ctypes.POINTER(AttnGrads), _I, _P, _SZ, _P])
-N.register("mtts_reduce_partials", ctypes.c_int, [_P, _I, _P])
-N.register("mtts_defer_reductions", None, [_I])
-N.register("mtts_pending_reductions", _I, [])
-N.register("mtts_flush_reductions", ctypes.c_int, [_P])
-N.register("mtts_discard_reductions", None, [])
-N.register("mtts_wgrad_plan_mode", None, [_I])
-N.register("mtts_wgrad_flush_cap", None, [_I])
-N.register("mtts_colsum_workspace_size", _SZ, [_I64, _I])
-N.register("mtts_colsum", ctypes.c_int, [_P, _I64, _I, _I, _P, _I, _P, _SZ, _P])
 
 
 # ------------------------------------------------------------------------------------------ helpers
@@ -1373,8 +1285,6 @@ def attention_tm(qkv, key_bias, heads: int, dropout_p: float = 0.0):
 # block's LayerNorm output (the q|k|v projection's A operand) and the FFN's d(pre-activation) (the dgrad
 # GEMM's A, the weight gradient's dY).  The backward adds the residual branch's gradient inside the
 # LayerNorm backward (mtts_layernorm_bwd_res) instead of an autograd accumulate kernel per sub-block.
-N.register("mtts_layernorm_bwd_res", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _SZ, _P])
-NORM_F_Y_BF16 = 0x100  # include/mtts_decoder.h MTTS_NORM_F_Y_BF16
 
 
 def _ln_fwd(h2, w, b, eps, y16):
@@ -1565,12 +1475,6 @@ def rope_tm(qkv, cos, sin, heads: int, rope_dims: int):
 
 
 # ------------------------------------------------------------------------------------------ step glue
-N.register("mtts_sequence_mask_f32", ctypes.c_int, [_P, _I, _I, _P, _P, _P])
-N.register("mtts_duration_loss_fwd", ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P])
-N.register("mtts_duration_loss_bwd", ctypes.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P])
-N.register("mtts_loss_sum", ctypes.c_int, [_P, _P, _P, _P, _P, _P])
-
-
 def _lengths64(lengths: torch.Tensor) -> torch.Tensor:
     return lengths if (lengths.dtype == torch.int64 and lengths.is_contiguous()) else lengths.to(torch.int64).contiguous()
 
@@ -1649,12 +1553,6 @@ def loss_sum(dur, prior, diff):
 
 
 # ------------------------------------------------------------------------------------------ time MLP
-N.register("mtts_rows_linear_workspace_size", _SZ, [_I, _I, _I, _P])
-N.register("mtts_rows_linear_fwd", ctypes.c_int, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _SZ, _P])
-N.register("mtts_rows_linear_bwd", ctypes.c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P])
-ROWS_ACT_NONE, ROWS_ACT_SILU, ROWS_ACT_MISH = 0, 1, 2  # include/mtts_decoder.h MTTS_ROWS_ACT_*
-
-
 def _ptrs(ts):
     return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
@@ -1675,7 +1573,6 @@ def _rows_ws(dev, B, K, ns):
     return t
 
 
-ROWS_MAX_MATS = 8  # include/mtts_decoder.h MTTS_ROWS_MAX_MATS: matrices per rows-linear launch
 
 
 def _chunks(n):

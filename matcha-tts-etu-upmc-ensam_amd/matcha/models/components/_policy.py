@@ -27,7 +27,8 @@ import os
 
 import torch
 
-PREC_FP32, PREC_BF16 = 0, 1
+from matcha._abi import MTTS_PREC_BF16 as PREC_BF16, MTTS_PREC_FP32 as PREC_FP32
+
 PACK_BF16_SPLIT = 2  # pack-cache kind: the bf16 hi + lo planes of a forward operand
 PACK_BF16_SPLIT3 = 3  # pack-cache kind: hi + mid + lo bf16 planes (== w exactly) of a bf16x6 forward operand
 

@@ -21,7 +21,6 @@ so no loss or gradient depends on them.  For the same reason residual adds use t
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -264,12 +263,6 @@ class _Embedding(torch.autograd.Function):
             N.check(N.lib().mtts_embedding_bwd(N.ptr(ids_c), N.ptr(gc), ids_c.numel(), V, C, ctx.scale, N.ptr(dw),
                                                st), "mtts_embedding_bwd")
         return None, dw, None
-
-
-N.register("mtts_embedding_fwd", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p])
-N.register("mtts_embedding_bwd", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p])
 
 
 class TextEncoder(nn.Module):

@@ -46,7 +46,6 @@ from __future__ import annotations
 
 import collections
 import contextlib
-import ctypes
 import math
 import os
 from dataclasses import dataclass
@@ -55,6 +54,7 @@ import torch
 import torch.distributed as dist
 
 from matcha import _native as N
+from matcha._abi import AdamWChunk as _AdamWChunk
 from matcha.models.components import _ops as OPS
 from matcha.models.components._defer import deferred_grad_sums
 from matcha.models.components._policy import trainer_precision
@@ -75,10 +75,6 @@ def synthetic_batch(B: int, Tx: int, Ty: int, n_feats: int = 80, seed: int = 0, 
     x = x * (pos_x < x_lengths[:, None])
     y = y * (pos_y < y_lengths[:, None, None])
     return {k: v.to(device) for k, v in dict(x=x, x_lengths=x_lengths, y=y, y_lengths=y_lengths).items()}
-
-
-class _AdamWChunk(ctypes.Structure):  # include/mtts_decoder.h mtts_adamw_chunk
-    _fields_ = [("grad", ctypes.c_void_p), ("offset", ctypes.c_int64), ("n", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
 class _FlatClipAdamW:
@@ -169,17 +165,6 @@ class _FlatClipAdamW:
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
             p.grad = None
-
-
-N.register("mtts_clip_adamw_workspace_size", ctypes.c_size_t, [ctypes.c_int32])
-N.register("mtts_clip_adamw", ctypes.c_int,
-           [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-            ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p])
-N.register("mtts_clip_adamw_scaled", ctypes.c_int,
-           [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-            ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-            ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p])
 
 
 @dataclass

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from matcha import _native as N
+from matcha._abi import MTTS_GL_HOP as GL_HOP, MTTS_GL_NFFT as GL_NFFT  # the one STFT geometry the kernels serve
 
 MAX_WAV_VALUE = 32768.0  # audio_process.py:9
 
@@ -252,7 +253,6 @@ class MelStatistics:
 
 
 # ---- mel -> waveform without a vocoder checkpoint (reference: generate.py:66-113) ----------------------------------
-GL_NFFT, GL_HOP = 1024, 256  # include/mtts_griffinlim.h: the one STFT geometry the kernels serve
 MEL_MIN_SAMPLES = (GL_NFFT - GL_HOP) // 2 + 1  # MelSpectrogram.batch: the shortest utterance a reflect pad by 384 accepts
 
 _gl_tables: dict = {}

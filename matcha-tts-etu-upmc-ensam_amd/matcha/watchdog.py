@@ -22,11 +22,6 @@ import time
 
 from matcha import _native as N
 
-N.register("mtts_dp_progress_create", ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p),
-                                                     ctypes.POINTER(ctypes.POINTER(ctypes.c_int32))])
-N.register("mtts_dp_progress_mark", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p])
-N.register("mtts_dp_progress_destroy", ctypes.c_int, [ctypes.c_void_p])
-
 
 class DeviceProgress:
     """Host-mapped progress slots written by the device in stream order (include/mtts_dp.h).  Slot 0: steps the

@@ -387,16 +387,8 @@ def test_bf16_operand_storage_bitwise(B, T, Cin, Cout, k, cfg):
 def test_reduce_partials_jobs():
     """csrc/reduce.hip against torch sums: plain and weight-layout jobs, float4 and scalar paths (n % 4),
     long narrow jobs (16 slices), accumulate, several jobs in one batched launch."""
-    import ctypes
-
     from matcha import _native as N
-    from matcha.models.components import _ops as O  # registers the entry points
-
-    class Job(ctypes.Structure):
-        _fields_ = [("part", ctypes.c_void_p), ("out", ctypes.c_void_p), ("stride", ctypes.c_int64),
-                    ("n", ctypes.c_int64), ("splits", ctypes.c_int32), ("accumulate", ctypes.c_int32),
-                    ("cols", ctypes.c_int32), ("cin", ctypes.c_int32), ("sr", ctypes.c_int64),
-                    ("sc", ctypes.c_int64), ("sj", ctypes.c_int64)]
+    from matcha._abi import ReduceJob as Job
 
     g = torch.Generator(device=DEV).manual_seed(5)
     cases = []  # (part [S, stride], out tensor, expected, job)
@@ -423,7 +415,6 @@ def test_reduce_partials_jobs():
     torch.cuda.synchronize()
     for p, o, e, _ in cases:
         torch.testing.assert_close(o, e, rtol=1e-5, atol=1e-4)
-    assert O is not None
 
 
 def _preln_inputs(B, T, C, heads, seed=0):

@@ -269,7 +269,6 @@ def test_rope_vector_and_scalar_kernels_bitwise(inverse):
     """The float4 RoPE kernel (16-byte aligned operands) and the scalar one (an unaligned view forces it)
     round identically -- the fp32 headline alignment is decided by ulp-level near-ties of mu_x."""
     from matcha import _native as N
-    from matcha.models.components import _ops as O  # noqa: F401  (registers the symbols)
     from matcha.models.components.text_encoder import RotaryPositionalEmbeddings
 
     B, T, H, d = 4, 61, 2, 96

@@ -68,7 +68,6 @@ def _plan(a, prec, cfg=-1, splits=0):
 
 def _ws(a, prec, cfg=-1, splits=0):
     from matcha import _native as N
-    from matcha.models.components import _ops as O  # registers the workspace query's signature  # noqa: F401
 
     return int(N.lib().mtts_conv_gemm_workspace_size(ctypes.byref(a), prec, cfg, splits))
 

@@ -42,7 +42,6 @@ main stream does with that memory after the fork, was not ordered before the sid
 the packed rows wider than their K are the transposed (dgrad) operands of an output count that is no multiple of
 8, which the one-channel `linear_tm` case below packs inside the poisoned run (N = 1 -> Kp = 8).
 """
-import ctypes
 import math
 
 import pytest
@@ -526,6 +525,7 @@ def test_wgrad_fp32():
 
 def test_colsum_and_reduce_partials():
     from matcha import _native as N
+    from matcha._abi import ReduceJob as Job
     from matcha.models.components import _ops as O
 
     lib = N.lib()
@@ -540,12 +540,6 @@ def test_colsum_and_reduce_partials():
         return [out]
 
     P.run_under_fills(colsum)
-
-    class Job(ctypes.Structure):
-        _fields_ = [("part", ctypes.c_void_p), ("out", ctypes.c_void_p), ("stride", ctypes.c_int64),
-                    ("n", ctypes.c_int64), ("splits", ctypes.c_int32), ("accumulate", ctypes.c_int32),
-                    ("cols", ctypes.c_int32), ("cin", ctypes.c_int32), ("sr", ctypes.c_int64),
-                    ("sc", ctypes.c_int64), ("sj", ctypes.c_int64)]
 
     g = _gen(5)  # the jobs of test_reduce_partials_jobs; the non-accumulating outputs come from torch.empty here
     p0, o0 = _r(g, 7, 1024), _r(g, 1024)
