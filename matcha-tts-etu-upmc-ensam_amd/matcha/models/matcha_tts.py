@@ -39,6 +39,7 @@ class MatchaTTS(BaseLightningClass):
     # None: the ambient default (_policy.parity_policy sets MTTS_PARITY_ENCODER's "fp32fwd", otherwise "bf16")
     encoder_precision = None
     last_seg = None  # forward(out_size=...) on the device: the windows of the last forward (see forward)
+    _config_hparams = ("encoder", "decoder", "cfm")  # load_from_checkpoint hands these back as Config trees
 
     @property
     def encoder_fp32(self) -> bool:
@@ -52,6 +53,12 @@ class MatchaTTS(BaseLightningClass):
                  out_size=None, optimizer=None, scheduler=None, prior_loss=True, use_precomputed_durations=False,
                  out_channels=None, hidden_channels=None):
         super().__init__()
+        # :79 / :110 -- everything load_from_checkpoint needs to rebuild this model, as plain values (config
+        # namespaces as dicts); optimizer / scheduler are factories, not state (the reference ignores them at :110)
+        self.save_hyperparameters(n_vocab=n_vocab, n_feats=n_feats, encoder=encoder, decoder=decoder, cfm=cfm,
+                                  data_statistics=data_statistics, out_size=out_size, prior_loss=prior_loss,
+                                  use_precomputed_durations=use_precomputed_durations, out_channels=out_channels,
+                                  hidden_channels=hidden_channels, logger=False)
         self.n_vocab = n_vocab
         self.n_spks = 1
         self.out_size = out_size

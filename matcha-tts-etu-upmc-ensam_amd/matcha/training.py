@@ -34,6 +34,11 @@ changes the padded-length dependent parts of the arithmetic (GroupNorm statistic
 frames).  agree_shapes=False lets each rank pad to its own length, as the reference's DDP would, and capture new
 shapes on its own (tested over gloo; not yet run with the in-graph RCCL transport on a multi-GPU box).
 
+Around the step, the rest of the reference's loop (Trainer.fit): validation_step / validate (eval(), no_grad(),
+captured per shape like the step), save_checkpoint / load_checkpoint (matcha/checkpoint.py: Lightning's file layout,
+the optimizer state in torch.optim.AdamW's form in both modes; a graph-mode load writes into the flat arrays in place,
+so captured steps stay valid), and per-epoch last / top-k checkpoints and resume.  None of it touches the step.
+
 Synthetic LJSpeech-shaped batches: token ids ~ U{1..149}, lengths ~ U[0.7 max, max]
 with element 0 = max, mels ~ N(0, 1) zeroed past the length.  A batch dict may carry "t" [B, 1, 1] and
 "z" [B, n_feats, Ty]: the CFM randomness injected for parity tests (MatchaTTS.forward's keywords); with
@@ -240,6 +245,8 @@ class Trainer:
         self._recorder = None
         self._arm = None  # (overlap,) while the reducer is to be armed in the next backward
         self._graphs = collections.OrderedDict()
+        self._val_graphs = collections.OrderedDict()  # validation_step's captures, an LRU of its own
+        self._best_k = {}  # fit's best checkpoints: file name -> loss/val (saved with every checkpoint)
         # bench.py's N>1 path (matcha/watchdog.py): a host watchdog told of every step / graph key / bucket issue,
         # and device progress markers captured into the step (one after each bucket's all-reduce, one at its end)
         self.watchdog = None
@@ -694,6 +701,220 @@ class Trainer:
         if self.scheduler is not None:
             self.scheduler.step()
         else:
-            c = self.cfg
-            lr = c.eta_min + (c.lr - c.eta_min) * (1 + math.cos(math.pi * self.epoch / c.t_max_epochs)) / 2
-            self.lr.fill_(lr)
+            self.lr.fill_(self.cosine_lr(self.epoch))
+
+    def cosine_lr(self, epoch: int) -> float:
+        """The schedule's closed form after `epoch` epochs (graph mode's lr; load_checkpoint restores lr with it)."""
+        c = self.cfg
+        return c.eta_min + (c.lr - c.eta_min) * (1 + math.cos(math.pi * epoch / c.t_max_epochs)) / 2
+
+    # ------------------------------------------------------------------------------------ validation
+    VAL_NAMES = ("sub_loss/val_dur_loss", "sub_loss/val_prior_loss", "sub_loss/val_diff_loss", "loss/val")
+    TRAIN_NAMES = ("sub_loss/train_dur_loss", "sub_loss/train_prior_loss", "sub_loss/train_diff_loss", "loss/train")
+
+    def _val_losses(self, batch):
+        """[dur, prior, diff, total] of one batch: the model's forward as the train step calls it (the batch's
+        "t" / "z" / "out_offset" / "durations" injected) under the trainer's precision context.  out_size as
+        get_losses applies it: TrainConfig.out_size, else the model's own."""
+        inject = {k: batch[k] for k in ("t", "z", "out_offset", "durations") if k in batch}
+        out_size = self.cfg.out_size if self.cfg.out_size is not None else getattr(self.model, "out_size", None)
+        if out_size is not None:
+            inject["out_size"] = out_size
+        with self._autocast():
+            dur, prior, diff, *_ = self.model(x=batch["x"], x_lengths=batch["x_lengths"], y=batch["y"],
+                                              y_lengths=batch["y_lengths"], **inject)
+        if dur.device.type == "cuda":
+            return OPS.loss_sum(dur, prior, diff)[1]
+        total = dur + prior + diff
+        return torch.stack([dur, torch.as_tensor(prior), diff, total]).float()
+
+    def _val_graph_step(self, batch):
+        """validation_step on the GPU in graph mode: the forward captured once per input-shape key (an LRU of its
+        own, TrainConfig.graph_cache entries: the train steps' captures are never evicted for it) and replayed
+        from static input buffers.  No gradient deferral is open here, so MatchaTTS.forward takes no prefetch
+        fork: the capture has one stream."""
+        key = tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(batch.items()))
+        e = self._val_graphs.get(key)
+        if e is None:
+            static = {k: v.clone() for k, v in batch.items()}
+            side = torch.cuda.Stream(self.dev)
+            side.wait_stream(torch.cuda.current_stream(self.dev))
+            with torch.cuda.stream(side):  # warm-up: allocator pools, pack plans, lazy loads
+                for _ in range(2):
+                    self._val_losses(static)
+            torch.cuda.current_stream(self.dev).wait_stream(side)
+            mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode=mode):
+                out = self._val_losses(static)
+            e = self._val_graphs[key] = {"g": g, "static": static, "out": out}
+            while len(self._val_graphs) > max(1, self.cfg.graph_cache):
+                self._val_graphs.popitem(last=False)
+        else:
+            self._val_graphs.move_to_end(key)
+        for k, v in e["static"].items():
+            if batch[k] is not v:
+                v.copy_(batch[k], non_blocking=True)
+        e["g"].replay()
+        return e["out"].clone()  # the next replay overwrites the graph's own output
+
+    def validation_step(self, batch: dict) -> torch.Tensor:
+        """The reference's validation_step (baselightningmodule.py:164-202) on one batch: the device tensor
+        [dur, prior, diff, total], computed under no_grad() with the model in eval() (dropout off, as
+        Lightning's validation loop sets it; every module's ``training`` flag is put back afterwards).  Touches
+        no parameter, gradient, optimizer state or global_step, and does not synchronise with the host."""
+        mods = list(self.model.modules())
+        flags = [m.training for m in mods]
+        # (a forward records how many dropout seeds it drew, to size the next one's pool: the train step's stays)
+        seeds = [(m, m.__dict__["_mtts_seed_count"]) for m in mods if "_mtts_seed_count" in m.__dict__]
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                if self.cfg.graph and self.dev.type == "cuda":
+                    return self._val_graph_step(batch)
+                return self._val_losses(batch)
+        finally:
+            for m, f in zip(mods, flags):
+                m.training = f
+            for m, n in seeds:
+                m.__dict__["_mtts_seed_count"] = n
+
+    def validate(self, batches) -> dict:
+        """The mean of validation_step over `batches` (and over ranks: the per-batch vectors are summed on the
+        device, the sum reduced ONCE over ranks -- the reference's sync_dist=True in one collective --, one host
+        sync at the end) under the reference's names: sub_loss/val_{dur,prior,diff}_loss and loss/val."""
+        acc = torch.zeros(5, dtype=torch.float32, device=self.dev)  # four sums and the batch count
+        for batch in batches:
+            acc[:4] += self.validation_step(batch)
+            acc[4] += 1
+        if self.world > 1:
+            dist.all_reduce(acc)
+        *sums, n = acc.tolist()
+        if n == 0:
+            raise ValueError("validate: no batches")
+        return {name: s / n for name, s in zip(self.VAL_NAMES, sums)}
+
+    # ------------------------------------------------------------------------------------ checkpoints
+    def save_checkpoint(self, path) -> None:
+        """One file in Lightning's layout (matcha/checkpoint.py): model, optimizer state in torch.optim.AdamW's
+        form (either mode), epoch, global_step, schedule, RNG states."""
+        from matcha import checkpoint as CK
+
+        CK.save(self, path)
+
+    def load_checkpoint(self, path) -> dict:
+        """Restores what save_checkpoint wrote, in place: in graph mode every address stays (flat parameter and
+        moment arrays, step counter, lr scalar -- lr recomputed from the epoch by on_epoch_end's formula), so
+        steps captured before the call stay valid; in eager mode the optimizer's and the scheduler's state_dict."""
+        from matcha import checkpoint as CK
+
+        ck = CK.load(self, path)
+        best = ck.get("callbacks", {}).get("best_k_models")
+        if best is not None:
+            self._best_k = {str(k): float(v) for k, v in best.items()}
+        return ck
+
+    # ------------------------------------------------------------------------------------ fit
+    def fit(self, train_batches, val_batches=None, *, max_epochs: int, ckpt_dir=None, save_top_k: int = 3,
+            save_last: bool = True, resume=None, log_every_n_steps: int = 10) -> list[dict]:
+        """The reference's loop (train.py:81-109 through Lightning's fit).  Per epoch: one step() per
+        cfg.accumulate_grad_batches micro-batches of train_batches (a trailing incomplete group is dropped),
+        then validate(val_batches), then on_epoch_end(), then the checkpoints in ckpt_dir:
+        ``last-epoch=EE-step=S.ckpt`` (replacing the previous last) and ``best-epoch=EE-loss_val=0.123.ckpt``,
+        of which the save_top_k with the lowest loss/val are kept (ModelCheckpoint(monitor="loss/val",
+        save_top_k=3) + save_last=True).  EE is the epoch that just ended, counted from 0.
+
+        train_batches / val_batches: a callable epoch -> iterable of batch dicts (a sampler's set_epoch goes
+        there), or a re-iterable.  resume: a checkpoint path, or True for find_latest_checkpoint(ckpt_dir);
+        training continues at the checkpoint's epoch.  The host waits for the device once every
+        log_every_n_steps steps (the four train losses) and once per
+        validation, never otherwise.  Every logged row is appended to the returned history and, with ckpt_dir,
+        written to ckpt_dir/metrics.csv (by rank 0)."""
+        import csv
+
+        from matcha.checkpoint import find_latest_checkpoint
+
+        rank0 = self.world == 1 or dist.get_rank() == 0
+        if ckpt_dir is not None:
+            ckpt_dir = os.fspath(ckpt_dir)
+            os.makedirs(ckpt_dir, exist_ok=True)
+        self._best_k = {}
+        if resume:
+            if resume is True and ckpt_dir is None:
+                raise ValueError("fit(resume=True) looks for the latest checkpoint in ckpt_dir")
+            path = find_latest_checkpoint(ckpt_dir) if resume is True else find_latest_checkpoint(checkpoint_path=resume)
+            if path is not None:
+                self.load_checkpoint(path)
+        if ckpt_dir is not None:  # best files that are gone (or another directory's) no longer count
+            self._best_k = {k: v for k, v in self._best_k.items() if os.path.exists(os.path.join(ckpt_dir, k))}
+        history: list[dict] = []
+        csv_path = os.path.join(ckpt_dir, "metrics.csv") if (ckpt_dir is not None and rank0) else None
+        rows, fields = [], []
+        if csv_path is not None and resume and os.path.exists(csv_path):
+            with open(csv_path, newline="") as f:
+                rd = csv.DictReader(f)
+                rows, fields = list(rd), list(rd.fieldnames or [])
+
+        def log(row):
+            history.append(row)
+            if csv_path is None:
+                return
+            rows.append(row)
+            new = [k for k in row if k not in fields]
+            if new or len(rows) == 1:  # a wider table: written again from the start
+                fields.extend(new)
+                with open(csv_path, "w", newline="") as f:
+                    w = csv.DictWriter(f, fieldnames=fields)
+                    w.writeheader()
+                    w.writerows(rows)
+            else:
+                with open(csv_path, "a", newline="") as f:
+                    csv.DictWriter(f, fieldnames=fields).writerow(row)
+
+        def batches_of(src, epoch):
+            return src(epoch) if callable(src) else src
+
+        last = None
+        if ckpt_dir is not None:
+            olds = sorted(f for f in os.listdir(ckpt_dir) if f.startswith("last-") and f.endswith(".ckpt"))
+            last = os.path.join(ckpt_dir, olds[-1]) if olds else None
+        n_acc = self.cfg.accumulate_grad_batches
+        while self.epoch < max_epochs:
+            epoch = self.epoch
+            micro = []
+            for batch in batches_of(train_batches, epoch):
+                micro.append(batch)
+                if len(micro) < n_acc:
+                    continue
+                logged = self.step(micro)
+                micro = []
+                if log_every_n_steps and self.global_step % log_every_n_steps == 0:
+                    row = {"epoch": epoch, "step": self.global_step, **dict(zip(self.TRAIN_NAMES, logged.tolist()))}
+                    log(row)
+            val = None
+            if val_batches is not None:
+                val = self.validate(batches_of(val_batches, epoch))
+                log({"epoch": epoch, "step": self.global_step, **val})
+            self.on_epoch_end()
+            if ckpt_dir is None:
+                continue
+            if val is not None and save_top_k:
+                name = f"best-epoch={epoch:02d}-loss_val={val['loss/val']:.3f}.ckpt"
+                ranked = sorted(list(self._best_k.items()) + [(name, val["loss/val"])], key=lambda kv: kv[1])
+                keep = dict(ranked[:save_top_k] if save_top_k > 0 else ranked)
+                dropped = [k for k in self._best_k if k not in keep]
+                self._best_k = keep
+                if name in keep:
+                    self.save_checkpoint(os.path.join(ckpt_dir, name))
+                if rank0:
+                    for k in dropped:
+                        with contextlib.suppress(FileNotFoundError):
+                            os.remove(os.path.join(ckpt_dir, k))
+            if save_last:
+                path = os.path.join(ckpt_dir, f"last-epoch={epoch:02d}-step={self.global_step}.ckpt")
+                self.save_checkpoint(path)
+                if rank0 and last is not None and last != path:
+                    with contextlib.suppress(FileNotFoundError):
+                        os.remove(last)
+                last = path
+        return history
