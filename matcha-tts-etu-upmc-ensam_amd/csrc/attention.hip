@@ -54,6 +54,42 @@ constexpr int kWaves = kThreads / 64;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr size_t kLdsMax = 160 * 1024;
 
+// -DMTTS_ATTN_TIMELINE=1 (diagnostic builds only, tools/r9/attn_timeline.py): lane 0 of every wave stamps the
+// 100 MHz wall clock into g_atl ([workgroup * 4 + wave][kAtlSlots]: kernel kind, entry, fragment loads issued,
+// first barrier passed, tile loop done, last store issued); read back by mtts_attn_timeline_read.  The short
+// dK/dV kernel stamps into the upper half of the buffer: it runs behind the short dQ kernel on the same grid.
+#ifndef MTTS_ATTN_TIMELINE
+#define MTTS_ATTN_TIMELINE 0
+#endif
+#if MTTS_ATTN_TIMELINE
+constexpr int kAtlSlots = 8, kAtlWaves = 16384;
+__device__ long long g_atl[kAtlWaves * kAtlSlots];
+#define MTTS_ATL_PUT(base, slot, value)                                                                            \
+    do {                                                                                                       \
+        const int tl_w = ((int)blockIdx.x + (int)gridDim.x * ((int)blockIdx.y + (int)gridDim.y * (int)blockIdx.z)) * \
+                             kWaves + (int)(threadIdx.x >> 6) + (base);                                        \
+        if ((threadIdx.x & 63) == 0 && tl_w < kAtlWaves) g_atl[tl_w * kAtlSlots + (slot)] = (value);           \
+    } while (0)
+#define MTTS_ATL_AT(base, slot) MTTS_ATL_PUT(base, slot, wall_clock64())
+#define MTTS_ATL(slot) MTTS_ATL_AT(0, slot)
+// kinds: 1 forward, 2 dQ, 3 dK/dV (both also as the roles of the merged launch), 4-6 their short kernels
+#define MTTS_ATL_ENTRY_AT(base, kind) \
+    do {                              \
+        MTTS_ATL_PUT(base, 0, kind);  \
+        MTTS_ATL_AT(base, 1);         \
+    } while (0)
+#define MTTS_ATL_ENTRY(kind) MTTS_ATL_ENTRY_AT(0, kind)
+#else
+#define MTTS_ATL_AT(base, slot) \
+    do {                        \
+    } while (0)
+#define MTTS_ATL(slot) MTTS_ATL_AT(0, slot)
+#define MTTS_ATL_ENTRY_AT(base, kind) \
+    do {                              \
+    } while (0)
+#define MTTS_ATL_ENTRY(kind) MTTS_ATL_ENTRY_AT(0, kind)
+#endif
+
 // Geometry per (precision, compiled head dim D in {32, 64, 96}; a runtime head dim dh <= D runs with
 // zero-filled columns dh..D-1).  Row tiles are [64 rows][D + pad] (fragment
 // reads along the head dim), transposed tiles [D][64 + pad] (fragment reads along the rows).
@@ -167,6 +203,45 @@ __device__ __forceinline__ float half_sum(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
+// Two 4-column groups of the lane's row, the lane's columns c0 + 4 lh.. (v0) and c1 + 4 lh.. (v1); lane l and
+// l ^ 32 hold the two halves of the same 8 columns of the same row.  bf16 storage with 16-byte aligned rows
+// (`wide`, wave-uniform): one v_permlane32_swap per dword hands the lower half-wave the upper's half of group 0
+// and the upper half-wave the lower's half of group 1, so each lane stores 8 columns as ONE 16-byte store (the
+// lower lanes c0.., the upper c1..) instead of two 8-byte ones -- the same bytes at the same addresses, half the
+// store instructions of an issue-bound tail.  Otherwise the 8-byte (bf16) / 16-byte (fp32) stores per group.
+// Columns at or past dh are not written (dh % 8 == 0: a group's halves are inside together).  Called by all
+// 64 lanes; `ok`: the lane's row exists.
+template <typename TI>
+__device__ __forceinline__ void st4f_pair(TI *row, bool ok, bool wide, int lh, int dh, int c0, float4 v0, int c1,
+                                          float4 v1) {
+    if constexpr (sizeof(TI) == 2) {
+        if (wide) {
+            const uint32_t a0 = pack2(v0.x, v0.y), a1 = pack2(v0.z, v0.w), b0 = pack2(v1.x, v1.y), b1 = pack2(v1.z, v1.w);
+            // -> [0]: lower lanes keep a, upper lanes get the lower's b; [1]: lower get the upper's a, upper keep b
+            const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+            const auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+            const int c = lh ? c1 : c0;
+            if (ok && c < dh) *reinterpret_cast<uint4 *>(row + c) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
+            return;
+        }
+    }
+    if (ok && c0 + 4 * lh < dh) st4f(row + c0 + 4 * lh, v0);
+    if (ok && c1 + 4 * lh < dh) st4f(row + c1 + 4 * lh, v1);
+}
+// bf16 rows whose every 8-column group starts 16-byte aligned (base and pitch; head offsets are multiples of 8)
+template <typename TI>
+__device__ __forceinline__ bool rows_aligned16(const TI *base, int ld) {
+    return sizeof(TI) == 2 && ((reinterpret_cast<uintptr_t>(base) | (uintptr_t)ld * sizeof(TI)) & 15) == 0;
+}
+
+// The thread id as a value the compiler cannot tie to its earlier uses: what an epilogue derives from it (lane
+// half, row) is recomputed there instead of being kept -- or spilled -- across the tile loop.
+__device__ __forceinline__ int fresh_tid() {
+    int t = (int)threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+}
+
 // 2^x as the bare v_exp_f32: arguments are <= kDefer or -inf (-> 0); tiny results flush to zero
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -174,20 +249,43 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 // dims in MFMA k-step order.
 template <bool BF16, int D>
 struct RowFrag;
+// The loads are unconditional, from addresses clamped into the row (`row` is a valid row of the batch even when
+// `ok` is false: the callers clamp it to row 0), and what lies outside (row past T, column past dh) is selected to
+// zero AFTER the load: no branch around a load, so a block's fragment loads are all in flight at once and the
+// first tile's loads join them (as TileLoader::load).  A raw chunk is the storage's own 4 elements.
+template <typename TI>
+struct RawChunk {
+    using type = std::conditional_t<sizeof(TI) == 4, float4, uint2>;
+};
+template <typename TI>
+__device__ __forceinline__ typename RawChunk<TI>::type ld4raw(const TI *p) {
+    return *reinterpret_cast<const typename RawChunk<TI>::type *>(p);
+}
+__device__ __forceinline__ float4 raw4f(float4 q, bool keep) { return keep ? q : make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float4 raw4f(uint2 q, bool keep) {
+    if (!keep) q = make_uint2(0u, 0u);
+    return make_float4(__uint_as_float(q.x << 16), __uint_as_float(q.x & 0xffff0000u), __uint_as_float(q.y << 16),
+                       __uint_as_float(q.y & 0xffff0000u));
+}
+
 template <int D>
 struct RowFrag<true, D> {
     bf16x8 f[D / 16];
     // mul: a prescale folded into the operand before its bf16 rounding (the softmax scale * log2 e)
     template <typename TI>
-    __device__ void load(const TI *row, bool ok, int lh, int dh, float mul = 1.f) {
+    __device__ __forceinline__ void load(const TI *row, bool ok, int lh, int dh, float mul = 1.f) {
+        typename RawChunk<TI>::type a[D / 16], b[D / 16];
+#pragma unroll
+        for (int ks = 0; ks < D / 16; ++ks) {  // dh % 8 == 0: the chunks at c and c + 4 are inside the row together
+            const int c = 16 * ks + 8 * lh, cc = c < dh ? c : 0;
+            a[ks] = ld4raw(row + cc);
+            b[ks] = ld4raw(row + cc + 4);
+        }
 #pragma unroll
         for (int ks = 0; ks < D / 16; ++ks) {
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-            const int c = 16 * ks + 8 * lh;
-            if (ok && c < dh) a = ld4f(row + c);
-            if (ok && c + 4 < dh) b = ld4f(row + c + 4);
-            const float e[8] = {a.x * mul, a.y * mul, a.z * mul, a.w * mul,
-                                b.x * mul, b.y * mul, b.z * mul, b.w * mul};
+            const bool keep = ok && 16 * ks + 8 * lh < dh;
+            const float4 x = raw4f(a[ks], keep), y = raw4f(b[ks], keep);
+            const float e[8] = {x.x * mul, x.y * mul, x.z * mul, x.w * mul, y.x * mul, y.y * mul, y.z * mul, y.w * mul};
             f[ks] = frag8(e);
         }
     }
@@ -195,9 +293,11 @@ struct RowFrag<true, D> {
 template <int D>
 struct RowFrag<false, D> {
     float f[D / 2];
-    __device__ void load(const float *row, bool ok, int lh, int dh, float = 1.f) {
+    __device__ __forceinline__ void load(const float *row, bool ok, int lh, int dh, float = 1.f) {
 #pragma unroll
-        for (int ks = 0; ks < D / 2; ++ks) f[ks] = (ok && 2 * ks + lh < dh) ? row[2 * ks + lh] : 0.f;
+        for (int ks = 0; ks < D / 2; ++ks) f[ks] = row[2 * ks + lh < dh ? 2 * ks + lh : 0];
+#pragma unroll
+        for (int ks = 0; ks < D / 2; ++ks) f[ks] = (ok && 2 * ks + lh < dh) ? f[ks] : 0.f;
     }
 };
 
@@ -368,6 +468,7 @@ __device__ __forceinline__ void tile_loop(int ntiles, Load &&load, Store &&store
     load(0);
     store(0);
     mtts::lds_barrier();
+    MTTS_ATL(3);
     for (int it = 0; it < ntiles; ++it) {
         const int buf = NB == 2 ? (it & 1) : 0;
         load((it + 1) * kTile);  // past the last tile every row is masked off (branch-free body)
@@ -412,6 +513,7 @@ __global__ __launch_bounds__(kThreads, (fwd_min_blocks<BF16, D, TI, DROP>())) vo
     const int b = bk_.z, h = bk_.y, T = p.T, dh = p.D;  // dh <= D: columns past dh are zero
     const int q = bk_.x * kRowsPerBlock + wave * 32 + lr;
     const bool q_ok = q < T;
+    MTTS_ATL_ENTRY(1);
     const TI *Kb = Kp + h * dh, *Vb = Vp + h * dh;
     const float c0 = key_bias_c0(p, b);
 
@@ -419,6 +521,7 @@ __global__ __launch_bounds__(kThreads, (fwd_min_blocks<BF16, D, TI, DROP>())) vo
     const float sl2 = p.scale * kLog2e;
     RowFrag<BF16, D> qf;
     qf.load(Qp + h * dh + ((size_t)b * T + (q_ok ? q : 0)) * p.ldq, q_ok, lh, dh, BF16 ? sl2 : 1.f);
+    MTTS_ATL(2);
 
     f32x16 acc[Gm::NT];
 #pragma unroll
@@ -525,38 +628,63 @@ __global__ __launch_bounds__(kThreads, (fwd_min_blocks<BF16, D, TI, DROP>())) vo
             body(buf, k0, std::false_type{});
     };
     tile_loop<NB>((T + kTile - 1) / kTile, load, store, compute);
+    MTTS_ATL(4);
 
-    if (q_ok) {
+    {
+        const int et = fresh_tid(), elh = (et >> 5) & 1, eq = bk_.x * kRowsPerBlock + (et >> 6) * 32 + (et & 31);
+        const bool eq_ok = eq < T;  // lh, q, q_ok again
         const float inv = 1.f / l;
-        TI *orow = Op + ((size_t)b * T + q) * p.ldo + h * dh;
+        TI *orow = Op + ((size_t)b * T + eq) * p.ldo + h * dh;
+        const bool wide = rows_aligned16(Op, p.ldo);
 #pragma unroll
         for (int t = 0; t < Gm::NT; ++t)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                if (t * 32 + 8 * g + 4 * lh < dh)
-                    st4f(orow + t * 32 + 8 * g + 4 * lh,
-                         make_float4(acc[t][4 * g] * inv, acc[t][4 * g + 1] * inv, acc[t][4 * g + 2] * inv,
-                                     acc[t][4 * g + 3] * inv));
-        if (lh == 0) p.lse[((size_t)b * p.H + h) * T + q] = m + log2f(l);
+            for (int g = 0; g < 4; g += 2)
+                st4f_pair(orow, eq_ok, wide, elh, dh, t * 32 + 8 * g,
+                          make_float4(acc[t][4 * g] * inv, acc[t][4 * g + 1] * inv, acc[t][4 * g + 2] * inv,
+                                      acc[t][4 * g + 3] * inv),
+                          t * 32 + 8 * g + 8,
+                          make_float4(acc[t][4 * g + 4] * inv, acc[t][4 * g + 5] * inv, acc[t][4 * g + 6] * inv,
+                                      acc[t][4 * g + 7] * inv));
+        if (eq_ok && elh == 0) p.lse[((size_t)b * p.H + h) * T + eq] = m + log2f(l);
     }
+    MTTS_ATL(5);
 }
 
 // ------------------------------------------------------------------------------------------------
 // dsum = rowsum(dO * O) over this lane's half of the head dims, then the two halves -- one function for
 // the dQ pass and the Drow pre-pass, so both form the same value
-template <int D, typename TI>
+// kBatch: float4 groups of both operands in flight at a time (0 = all: inside the dQ pass, whose registers are
+// idle in the prologue; the stand-alone pre-pass runs batches of 4, at which every instance stays at 8 waves)
+template <int D, int kBatchArg = 0, typename TI>
 __device__ __forceinline__ float row_dot(const TI *orow, const TI *grow, int lh, int dh, bool ok) {
+    // unconditional loads from clamped columns (as RowFrag::load; the callers clamp the row); a group past dh or
+    // of a row past T is selected to zero in the loaded bits (a select on the sum instead lets the compiler sink
+    // the loads back under a branch) and adds +0 to the sum, which leaves it bit for bit what skipping the group
+    // left (the sum starts at +0 and is never -0)
+    constexpr int kGroups = D / 8, kBatch = kBatchArg > 0 ? kBatchArg : kGroups;
+    static_assert(kGroups % kBatch == 0, "row_dot: whole batches");
     float dsum = 0.f;
-    if (ok) {
-        orow += (D / 2) * lh;
-        grow += (D / 2) * lh;
+    auto batch = [&](int i0) __attribute__((always_inline)) {
+        typename RawChunk<TI>::type a[kBatch], c[kBatch];
 #pragma unroll
-        for (int i = 0; i < D / 2; i += 4) {
-            if ((D / 2) * lh + i >= dh) break;
-            const float4 a = ld4f(orow + i);
-            const float4 c = ld4f(grow + i);
-            dsum += a.x * c.x + a.y * c.y + a.z * c.z + a.w * c.w;
+        for (int i = 0; i < kBatch; ++i) {
+            const int col = (D / 2) * lh + 4 * (i0 + i), cc = col < dh ? col : 0;
+            a[i] = ld4raw(orow + cc);
+            c[i] = ld4raw(grow + cc);
         }
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) {
+            const bool keep = ok && (D / 2) * lh + 4 * (i0 + i) < dh;  // both operands zeroed: the group sums to +0
+            const float4 x = raw4f(a[i], keep), y = raw4f(c[i], keep);
+            dsum += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
+        }
+    };
+    if constexpr (kBatch == kGroups) {
+        batch(0);
+    } else {  // a rolled loop: the compiler cannot lift the next batch's loads (and their registers) over this one
+#pragma nounroll
+        for (int i0 = 0; i0 < kGroups; i0 += kBatch) batch(i0);
     }
     return half_sum(dsum);
 }
@@ -586,6 +714,7 @@ __device__ __forceinline__ void bwd_dq_body(const mtts_attn_args &p, const mtts_
     const int q = bx * kRowsPerBlock + wave * 32 + lr;
     const bool q_ok = q < T;
     const size_t qrow = (size_t)b * T + (q_ok ? q : 0);
+    MTTS_ATL_ENTRY(2);
     const TI *Kb = Kp + h * dh, *Vb = Vp + h * dh;
 
     const float sl2 = p.scale * kLog2e, c0 = key_bias_c0(p, b);
@@ -595,8 +724,10 @@ __device__ __forceinline__ void bwd_dq_body(const mtts_attn_args &p, const mtts_
     // Drow[q] = sum_d dO[q,d] * O[q,d]: each half-wave lane sums D/2 dims
     const float dsum = row_dot<D>(Op + qrow * p.ldo + h * dh, Gp + qrow * g.lddo + h * dh, lh, dh, q_ok);
     const size_t srow = ((size_t)b * p.H + h) * T + (q_ok ? q : 0);
-    const float lse2 = q_ok ? p.lse[srow] : 0.f;
+    const float lse_raw = p.lse[srow];  // srow is clamped: no branch around the load
+    const float lse2 = q_ok ? lse_raw : 0.f;
     if (Drow && q_ok && lh == 0) Drow[srow] = dsum;
+    MTTS_ATL(2);
 
     f32x16 acc[Gm::NT];
 #pragma unroll
@@ -670,19 +801,24 @@ __device__ __forceinline__ void bwd_dq_body(const mtts_attn_args &p, const mtts_
             body(buf, k0, std::false_type{});
     };
     tile_loop<NB>((T + kTile - 1) / kTile, load, store, compute);
+    MTTS_ATL(4);
 
-    if (q_ok) {
+    {
         TI *drow = DQp + ((size_t)b * T + q) * g.ldd + h * dh;
         const float sc = p.scale;
+        const bool wide = rows_aligned16(DQp, g.ldd);
 #pragma unroll
         for (int t = 0; t < Gm::NT; ++t)
 #pragma unroll
-            for (int gi = 0; gi < 4; ++gi)
-                if (t * 32 + 8 * gi + 4 * lh < dh)
-                    st4f(drow + t * 32 + 8 * gi + 4 * lh,
-                         make_float4(acc[t][4 * gi] * sc, acc[t][4 * gi + 1] * sc, acc[t][4 * gi + 2] * sc,
-                                     acc[t][4 * gi + 3] * sc));
+            for (int gi = 0; gi < 4; gi += 2)
+                st4f_pair(drow, q_ok, wide, lh, dh, t * 32 + 8 * gi,
+                          make_float4(acc[t][4 * gi] * sc, acc[t][4 * gi + 1] * sc, acc[t][4 * gi + 2] * sc,
+                                      acc[t][4 * gi + 3] * sc),
+                          t * 32 + 8 * gi + 8,
+                          make_float4(acc[t][4 * gi + 4] * sc, acc[t][4 * gi + 5] * sc, acc[t][4 * gi + 6] * sc,
+                                      acc[t][4 * gi + 7] * sc));
     }
+    MTTS_ATL(5);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -710,14 +846,17 @@ __device__ __forceinline__ void bwd_dkv_body(const mtts_attn_args &p, const mtts
     const int key = bx * kRowsPerBlock + wave * 32 + lr;
     const bool k_ok = key < T;
     const size_t krow = (size_t)b * T + (k_ok ? key : 0);
+    MTTS_ATL_ENTRY(3);
 
     const float sl2 = p.scale * kLog2e, c0 = key_bias_c0(p, b);
     RowFrag<BF16, D> kf, vf;
     kf.load(Kp + h * dh + krow * p.ldq, k_ok, lh, dh, BF16 ? sl2 : 1.f);  // bf16: S in the log2 domain
     vf.load(Vp + h * dh + krow * p.ldq, k_ok, lh, dh);
-    const float bias2 = (k_ok && p.key_bias) ? (p.key_bias[krow] - c0) * kLog2e : 0.f;
+    const float bias_raw = *(p.key_bias ? p.key_bias + krow : p.q);  // krow is clamped (as stage_bias)
+    const float bias2 = (k_ok && p.key_bias) ? (bias_raw - c0) * kLog2e : 0.f;
     const TI *Qb = Qp + h * dh, *Gb = Gp + h * dh;
     const size_t sbase = ((size_t)b * p.H + h) * T;
+    MTTS_ATL(2);
 
     f32x16 dk[Gm::NT], dv[Gm::NT];
 #pragma unroll
@@ -797,22 +936,30 @@ __device__ __forceinline__ void bwd_dkv_body(const mtts_attn_args &p, const mtts
         }
     };
     tile_loop<NB>((T + kTile - 1) / kTile, load, store, compute);
+    MTTS_ATL(4);
 
-    if (k_ok) {
+    {
         TI *dkr = DKp + krow * g.ldd + h * dh;
         TI *dvr = DVp + krow * g.ldd + h * dh;
         const float sc = p.scale;
+        const bool wide = rows_aligned16(DKp, g.ldd) && rows_aligned16(DVp, g.ldd);
 #pragma unroll
         for (int t = 0; t < Gm::NT; ++t)
 #pragma unroll
-            for (int gi = 0; gi < 4; ++gi) {
-                const int c = t * 32 + 8 * gi + 4 * lh;
-                if (c >= dh) continue;
-                st4f(dkr + c, make_float4(dk[t][4 * gi] * sc, dk[t][4 * gi + 1] * sc, dk[t][4 * gi + 2] * sc,
-                                          dk[t][4 * gi + 3] * sc));
-                st4f(dvr + c, make_float4(dv[t][4 * gi], dv[t][4 * gi + 1], dv[t][4 * gi + 2], dv[t][4 * gi + 3]));
+            for (int gi = 0; gi < 4; gi += 2) {
+                const int c = t * 32 + 8 * gi;
+                st4f_pair(dkr, k_ok, wide, lh, dh, c,
+                          make_float4(dk[t][4 * gi] * sc, dk[t][4 * gi + 1] * sc, dk[t][4 * gi + 2] * sc,
+                                      dk[t][4 * gi + 3] * sc),
+                          c + 8,
+                          make_float4(dk[t][4 * gi + 4] * sc, dk[t][4 * gi + 5] * sc, dk[t][4 * gi + 6] * sc,
+                                      dk[t][4 * gi + 7] * sc));
+                st4f_pair(dvr, k_ok, wide, lh, dh, c,
+                          make_float4(dv[t][4 * gi], dv[t][4 * gi + 1], dv[t][4 * gi + 2], dv[t][4 * gi + 3]), c + 8,
+                          make_float4(dv[t][4 * gi + 4], dv[t][4 * gi + 5], dv[t][4 * gi + 6], dv[t][4 * gi + 7]));
             }
     }
+    MTTS_ATL(5);
 }
 
 template <bool BF16, int D, typename TI = float, bool DROP = true>
@@ -836,7 +983,7 @@ __global__ __launch_bounds__(kThreads) void attn_drow_kernel(mtts_attn_args p, m
     const int q = bk_.x * kRowsPerBlock + wave * 32 + lr;
     const bool q_ok = q < T;
     const size_t qrow = (size_t)b * T + (q_ok ? q : 0);
-    const float dsum = row_dot<D>(Op + qrow * p.ldo + h * dh, Gp + qrow * g.lddo + h * dh, lh, dh, q_ok);
+    const float dsum = row_dot<D, 4>(Op + qrow * p.ldo + h * dh, Gp + qrow * g.lddo + h * dh, lh, dh, q_ok);
     if (q_ok && lh == 0) Drow[((size_t)b * p.H + h) * T + q] = dsum;
 }
 
@@ -957,15 +1104,18 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_short_kernel(mtts_attn_args
     const int q = bk_.x * kShortRows + lr;
     const bool q_ok = q < T;
     const int buf = wave >> 1, sub = wave & 1;
+    MTTS_ATL_ENTRY(4);
     const float c0 = key_bias_c0(p, b), sl2 = p.scale * kLog2e;
 
     RowFrag<BF16, D> qf;
     qf.load(Qp + h * dh + ((size_t)b * T + (q_ok ? q : 0)) * p.ldq, q_ok, lh, dh, BF16 ? sl2 : 1.f);
+    MTTS_ATL(2);
     const float br0 = stage_bias(p, b, tid & (kTile - 1), c0), br1 = stage_bias(p, b, kTile + (tid & (kTile - 1)), c0);
     stage_pair<BF16, D>(Kp + h * dh, Vp + h * dh, p.ldq, p.ldq, b, T, tid, dh, Ks, Vs);
     store_bias(bias_s, flag_s, 0, br0, tid);
     store_bias(bias_s, flag_s, 1, br1, tid);
     mtts::lds_barrier();
+    MTTS_ATL(3);
 
     f32x16 acc[Gm::NT];
 #pragma unroll
@@ -1009,6 +1159,7 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_short_kernel(mtts_attn_args
 #pragma unroll
         for (int t = 0; t < Gm::NT; ++t) mma_perm_r<BF16, D>(acc[t], V_, t * 32 + lr, sub, lh, s);
     }
+    MTTS_ATL(4);
     mtts::lds_barrier();  // the staged tiles are dead: the merge area may overwrite them
     if (lh == 0) {
         ms[wave * 32 + lr] = m;
@@ -1025,18 +1176,26 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_short_kernel(mtts_attn_args
         wgt[w] = mw == -INFINITY ? 0.f : fast_exp2(mw - M);
         L += wgt[w] * ls[w * 32 + lr];
     }
-    if (q_ok) {
+    {
         const float inv = 1.f / L;
         TI *orow = Op + ((size_t)b * T + q) * p.ldo + h * dh;
+        const bool wide = rows_aligned16(Op, p.ldo);
 #pragma unroll
-        for (int t = 0; t < Gm::NT; ++t) {
-            const int c = t * 32 + 8 * wave + 4 * lh;  // wave w writes the C-layout group g = w
-            if (c >= dh) continue;
-            const float4 o = sum_partials<Gm::NT>(area, t, wave, lane, wgt);
-            st4f(orow + c, make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv));
+        for (int t = 0; t < Gm::NT; t += 2) {  // wave w writes the C-layout group g = w of every 32-column tile
+            const int c0 = t * 32 + 8 * wave;
+            const float4 o0 = sum_partials<Gm::NT>(area, t, wave, lane, wgt);
+            float4 o1 = o0;
+            int c1 = D;  // an odd last tile has no partner: a column past dh, never written
+            if (t + 1 < Gm::NT) {
+                o1 = sum_partials<Gm::NT>(area, t + 1, wave, lane, wgt);
+                c1 = c0 + 32;
+            }
+            st4f_pair(orow, q_ok, wide, lh, dh, c0, make_float4(o0.x * inv, o0.y * inv, o0.z * inv, o0.w * inv), c1,
+                      make_float4(o1.x * inv, o1.y * inv, o1.z * inv, o1.w * inv));
         }
-        if (wave == 0 && lh == 0) p.lse[((size_t)b * p.H + h) * T + q] = M + log2f(L);
+        if (q_ok && wave == 0 && lh == 0) p.lse[((size_t)b * p.H + h) * T + q] = M + log2f(L);
     }
+    MTTS_ATL(5);
 }
 
 // backward dQ: grid (ceil(T/32), H, B); lane = query, wave = key sub-tile.  Writes Drow as well.
@@ -1063,33 +1222,28 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dq_short_kernel(mtts_attn_a
     const bool q_ok = q < T;
     const size_t qrow = (size_t)b * T + (q_ok ? q : 0);
     const int buf = wave >> 1, sub = wave & 1;
+    MTTS_ATL_ENTRY(5);
     const float sl2 = p.scale * kLog2e, c0 = key_bias_c0(p, b);
 
     RowFrag<BF16, D> qf, gf;
     qf.load(Qp + h * dh + qrow * p.ldq, q_ok, lh, dh, BF16 ? sl2 : 1.f);
     gf.load(Gp + h * dh + qrow * g.lddo, q_ok, lh, dh);
-    float dsum = 0.f;  // rowsum(dO * O), as the long dQ kernel (every wave: the same query per lane)
-    if (q_ok) {
-        const TI *orow = Op + qrow * p.ldo + h * dh + (D / 2) * lh;
-        const TI *grow = Gp + qrow * g.lddo + h * dh + (D / 2) * lh;
-#pragma unroll
-        for (int i = 0; i < D / 2; i += 4) {
-            if ((D / 2) * lh + i >= dh) break;
-            const float4 a = ld4f(orow + i);
-            const float4 c = ld4f(grow + i);
-            dsum += a.x * c.x + a.y * c.y + a.z * c.z + a.w * c.w;
-        }
-    }
-    dsum = half_sum(dsum);
+    // rowsum(dO * O), as the long dQ kernel (every wave: the same query per lane); fp32 at D = 32 in two batches:
+    // with all four groups in flight the kernel needs 132 registers and loses its fourth workgroup per CU
+    const float dsum = row_dot<D, (D == 32 && sizeof(TI) == 4) ? 2 : 0>(Op + qrow * p.ldo + h * dh,
+                                                                         Gp + qrow * g.lddo + h * dh, lh, dh, q_ok);
     const size_t srow = ((size_t)b * p.H + h) * T + (q_ok ? q : 0);
-    const float lse2 = q_ok ? p.lse[srow] : 0.f;
+    const float lse_raw = p.lse[srow];  // srow is clamped: no branch around the load
+    const float lse2 = q_ok ? lse_raw : 0.f;
     if (q_ok && wave == 0 && lh == 0) Drow[srow] = dsum;
+    MTTS_ATL(2);
 
     const float br0 = stage_bias(p, b, tid & (kTile - 1), c0), br1 = stage_bias(p, b, kTile + (tid & (kTile - 1)), c0);
     stage_pair<BF16, D>(Kp + h * dh, Vp + h * dh, p.ldq, p.ldq, b, T, tid, dh, Ks, Vs);
     store_bias(bias_s, flag_s, 0, br0, tid);
     store_bias(bias_s, flag_s, 1, br1, tid);
     mtts::lds_barrier();
+    MTTS_ATL(3);
 
     f32x16 acc[Gm::NT];
 #pragma unroll
@@ -1131,21 +1285,30 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dq_short_kernel(mtts_attn_a
 #pragma unroll
         for (int t = 0; t < Gm::NT; ++t) mma_perm_r<BF16, D>(acc[t], K_, t * 32 + lr, sub, lh, ds);  // dQ^T += K^T dS^T
     }
+    MTTS_ATL(4);
     mtts::lds_barrier();
     put_partial<Gm::NT>(area, acc, wave, lane);
     mtts::lds_barrier();
-    if (q_ok) {
+    {
         const float one[kWaves] = {1.f, 1.f, 1.f, 1.f};
         TI *drow = DQp + ((size_t)b * T + q) * g.ldd + h * dh;
         const float sc = p.scale;
+        const bool wide = rows_aligned16(DQp, g.ldd);
 #pragma unroll
-        for (int t = 0; t < Gm::NT; ++t) {
-            const int c = t * 32 + 8 * wave + 4 * lh;
-            if (c >= dh) continue;
-            const float4 o = sum_partials<Gm::NT>(area, t, wave, lane, one);
-            st4f(drow + c, make_float4(o.x * sc, o.y * sc, o.z * sc, o.w * sc));
+        for (int t = 0; t < Gm::NT; t += 2) {  // tiles in pairs, as the short forward
+            const int c0 = t * 32 + 8 * wave;
+            const float4 o0 = sum_partials<Gm::NT>(area, t, wave, lane, one);
+            float4 o1 = o0;
+            int c1 = D;
+            if (t + 1 < Gm::NT) {
+                o1 = sum_partials<Gm::NT>(area, t + 1, wave, lane, one);
+                c1 = c0 + 32;
+            }
+            st4f_pair(drow, q_ok, wide, lh, dh, c0, make_float4(o0.x * sc, o0.y * sc, o0.z * sc, o0.w * sc), c1,
+                      make_float4(o1.x * sc, o1.y * sc, o1.z * sc, o1.w * sc));
         }
     }
+    MTTS_ATL(5);
 }
 
 // backward dK/dV: grid (ceil(T/32), H, B); lane = key, wave = query sub-tile
@@ -1173,25 +1336,26 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkv_short_kernel(mtts_attn_
     const bool k_ok = key < T;
     const size_t krow = (size_t)b * T + (k_ok ? key : 0);
     const int buf = wave >> 1, sub = wave & 1;
+    MTTS_ATL_ENTRY_AT(kAtlWaves / 2, 6);
     const float sl2 = p.scale * kLog2e, c0 = key_bias_c0(p, b);
 
     RowFrag<BF16, D> kf, vf;
     kf.load(Kp + h * dh + krow * p.ldq, k_ok, lh, dh, BF16 ? sl2 : 1.f);
     vf.load(Vp + h * dh + krow * p.ldq, k_ok, lh, dh);
-    const float bias2 = (k_ok && p.key_bias) ? (p.key_bias[krow] - c0) * kLog2e : 0.f;
+    const float bias_raw = *(p.key_bias ? p.key_bias + krow : p.q);  // krow is clamped (as stage_bias)
+    const float bias2 = (k_ok && p.key_bias) ? (bias_raw - c0) * kLog2e : 0.f;
     const size_t sbase = ((size_t)b * p.H + h) * T;
-    float lse_r = 0.f, d_r = 0.f;
-    if (tid < kShortT) {
-        const float l_raw = p.lse[sbase + min(tid, T - 1)], d_raw = Drow[sbase + min(tid, T - 1)];
-        lse_r = tid < T ? l_raw : INFINITY;
-        d_r = tid < T ? d_raw : 0.f;
-    }
+    MTTS_ATL_AT(kAtlWaves / 2, 2);
+    // every thread loads (clamped index; threads past kShortT store nothing): no branch around the loads
+    const float l_raw = p.lse[sbase + min(tid, T - 1)], d_raw = Drow[sbase + min(tid, T - 1)];
+    const float lse_r = tid < T ? l_raw : INFINITY, d_r = tid < T ? d_raw : 0.f;
     stage_pair<BF16, D>(Qp + h * dh, Gp + h * dh, p.ldq, g.lddo, b, T, tid, dh, Qs, Gs);
     if (tid < kShortT) {
         lse_s[tid] = lse_r;
         d_s[tid] = d_r;
     }
     mtts::lds_barrier();
+    MTTS_ATL_AT(kAtlWaves / 2, 3);
 
     f32x16 dk[Gm::NT], dv[Gm::NT];
 #pragma unroll
@@ -1238,25 +1402,35 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkv_short_kernel(mtts_attn_
             mma_perm_r<BF16, D>(dk[t], Q_, t * 32 + lr, sub, lh, ds);  // dK^T += Q^T dS
         }
     }
+    MTTS_ATL_AT(kAtlWaves / 2, 4);
     mtts::lds_barrier();
     put_partial<Gm::NT>(area_k, dk, wave, lane);
     put_partial<Gm::NT>(area_v, dv, wave, lane);
     mtts::lds_barrier();
-    if (k_ok) {
+    {
         const float one[kWaves] = {1.f, 1.f, 1.f, 1.f};
         TI *dkr = DKp + krow * g.ldd + h * dh;
         TI *dvr = DVp + krow * g.ldd + h * dh;
         const float sc = p.scale;
+        const bool wide = rows_aligned16(DKp, g.ldd) && rows_aligned16(DVp, g.ldd);
 #pragma unroll
-        for (int t = 0; t < Gm::NT; ++t) {
-            const int c = t * 32 + 8 * wave + 4 * lh;
-            if (c >= dh) continue;
-            const float4 a = sum_partials<Gm::NT>(area_k, t, wave, lane, one);
-            const float4 e = sum_partials<Gm::NT>(area_v, t, wave, lane, one);
-            st4f(dkr + c, make_float4(a.x * sc, a.y * sc, a.z * sc, a.w * sc));
-            st4f(dvr + c, e);
+        for (int t = 0; t < Gm::NT; t += 2) {  // tiles in pairs, as the short forward
+            const int c0 = t * 32 + 8 * wave;
+            const float4 a0 = sum_partials<Gm::NT>(area_k, t, wave, lane, one);
+            const float4 e0 = sum_partials<Gm::NT>(area_v, t, wave, lane, one);
+            float4 a1 = a0, e1 = e0;
+            int c1 = D;
+            if (t + 1 < Gm::NT) {
+                a1 = sum_partials<Gm::NT>(area_k, t + 1, wave, lane, one);
+                e1 = sum_partials<Gm::NT>(area_v, t + 1, wave, lane, one);
+                c1 = c0 + 32;
+            }
+            st4f_pair(dkr, k_ok, wide, lh, dh, c0, make_float4(a0.x * sc, a0.y * sc, a0.z * sc, a0.w * sc), c1,
+                      make_float4(a1.x * sc, a1.y * sc, a1.z * sc, a1.w * sc));
+            st4f_pair(dvr, k_ok, wide, lh, dh, c0, e0, c1, e1);
         }
     }
+    MTTS_ATL_AT(kAtlWaves / 2, 5);
 }
 
 // the short path is the default for T <= 128; MTTS_ATTN_SHORT=0 sends every shape down the long one
@@ -1469,6 +1643,20 @@ int mtts_attention_fwd(const mtts_attn_args *p, int32_t precision, void *hip_str
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     return precision == MTTS_PREC_BF16 ? fwd_dispatch<true>(*p, st) : fwd_dispatch<false>(*p, st);
 }
+
+#if MTTS_ATTN_TIMELINE
+// diagnostic builds: copy (or zero, host == NULL) the attention kernels' timeline buffer; returns its size in bytes
+long long mtts_attn_timeline_read(void *host) {
+    const size_t bytes = sizeof(long long) * kAtlWaves * kAtlSlots;
+    if (host) {
+        if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_atl), bytes) != hipSuccess) return -1;
+    } else {
+        void *d = nullptr;
+        if (hipGetSymbolAddress(&d, HIP_SYMBOL(g_atl)) != hipSuccess || hipMemset(d, 0, bytes) != hipSuccess) return -1;
+    }
+    return (long long)bytes;
+}
+#endif
 
 size_t mtts_attention_bwd_workspace_size(int32_t B, int32_t T, int32_t H) {
     return mtts::align_up((size_t)B * H * T * sizeof(float), 256);
