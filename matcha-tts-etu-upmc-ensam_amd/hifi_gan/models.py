@@ -16,6 +16,7 @@ import torch
 from torch import nn
 from torch.nn.utils import remove_weight_norm, weight_norm
 
+from matcha import _graphs as G
 from matcha import _native as N
 
 from . import ops as V
@@ -86,6 +87,7 @@ class Generator(nn.Module):
     is no multiple of 8) raises ValueError here, not at the first launch."""
 
     # the whole forward of one (B, T) is captured once into a HIP graph and replayed; bounded cache
+    # (matcha/_graphs.py), a fresh one whenever the weights are repacked
     graph: bool = True
     _GRAPH_CACHE_MAX = 8
 
@@ -159,7 +161,7 @@ class Generator(nn.Module):
                       for pair in rb.pairs()] for rb in self.resblocks]
         pk["post"] = (V.pack_post(self._folded(self.conv_post)), f32(self.conv_post.bias))
         self.__dict__["_pack"] = pk
-        self.__dict__["_graphs"] = {}  # captured graphs hold the old buffers
+        self.__dict__["_graphs"] = G.GraphCache(self._GRAPH_CACHE_MAX)  # captured graphs hold the old buffers
         return pk
 
     # ---- forward --------------------------------------------------------------------------------------------
@@ -178,26 +180,13 @@ class Generator(nn.Module):
             return self._forward_eager(mel, pk)
 
     def _forward_graph(self, mel, pk):
-        cache = self.__dict__.setdefault("_graphs", {})
-        key = (tuple(mel.shape), mel.device)
-        ent = cache.get(key)
-        if ent is None:
-            if len(cache) >= self._GRAPH_CACHE_MAX:
-                cache.pop(next(iter(cache)))
+        def build():
             with torch.inference_mode(False):  # a later call outside inference mode still copies into it
                 smel = torch.empty(mel.shape, device=mel.device, dtype=torch.float32)
             smel.copy_(mel)
-            cur = torch.cuda.current_stream(mel.device)
-            side = torch.cuda.Stream(mel.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):  # warm-up: lazy code-object loads, allocator pools
-                self._forward_eager(smel, pk)
-            cur.wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out = self._forward_eager(smel, pk)
-            ent = cache[key] = (g, smel, out)
-        g, smel, out = ent
+            return smel, *G.capture(lambda: self._forward_eager(smel, pk), mel.device)
+
+        smel, g, out = self._graphs.lookup((tuple(mel.shape), mel.device), build)
         smel.copy_(mel)
         g.replay()
         return out.clone()

@@ -13,6 +13,7 @@ from abc import ABC
 import torch
 import torch.nn as nn
 
+from matcha import _graphs as G
 from matcha import _native as N
 from matcha.models.components import _defer as D
 from matcha.models.components.decoder import Decoder
@@ -128,7 +129,7 @@ class BaseConditionalFlowMatching(nn.Module, ABC):
         return self.solve_ode_euler(z, t_span, mu, mask, spks, cond)
 
     # the whole Euler solve of one (shape, n_timesteps) is captured once into a HIP graph and replayed:
-    # n_timesteps decoder forwards (~70 kernels each) become one graph launch.  Bounded cache.
+    # n_timesteps decoder forwards (~70 kernels each) become one graph launch.  Bounded cache (matcha/_graphs.py).
     graph_ode: bool = True
     _GRAPH_CACHE_MAX = 8
 
@@ -141,29 +142,17 @@ class BaseConditionalFlowMatching(nn.Module, ABC):
         return self._solve_eager(x, t_span, mu, mask)
 
     def _solve_graph(self, x, t_span, mu, mask):
-        cache = self.__dict__.setdefault("_ode_graphs", {})
+        cache = self.__dict__.setdefault("_ode_graphs", G.GraphCache(self._GRAPH_CACHE_MAX))
         key = (tuple(x.shape), tuple(mu.shape), t_span.numel(), x.dtype, x.device,
                torch.is_autocast_enabled("cuda"), torch.get_autocast_dtype("cuda"))
-        ent = cache.get(key)
-        if ent is None:
-            if len(cache) >= self._GRAPH_CACHE_MAX:
-                cache.pop(next(iter(cache)))
-            sx, smu, sm, st = x.clone(), mu.clone(), mask.clone(), t_span.clone()
-            cur = torch.cuda.current_stream(x.device)
-            side = torch.cuda.Stream(x.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):  # warm-up: lazy loads, pack plans, allocator pools
-                self._solve_eager(sx, st, smu, sm)
-            cur.wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out = self._solve_eager(sx, st, smu, sm)
-            ent = cache[key] = (g, sx, smu, sm, st, out)
-        g, sx, smu, sm, st, out = ent
-        sx.copy_(x)
-        smu.copy_(mu)
-        sm.copy_(mask)
-        st.copy_(t_span)
+
+        def build():
+            static = (x.clone(), t_span.clone(), mu.clone(), mask.clone())
+            return static, *G.capture(lambda: self._solve_eager(*static), x.device)
+
+        static, g, out = cache.lookup(key, build)
+        for s, v in zip(static, (x, t_span, mu, mask)):
+            s.copy_(v)
         g.replay()
         return out.clone()
 

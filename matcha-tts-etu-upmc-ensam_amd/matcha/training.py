@@ -49,7 +49,6 @@ duration_path launch in place of the MAS kernels, and a replay reads the batch's
 """
 from __future__ import annotations
 
-import collections
 import contextlib
 import math
 import os
@@ -58,6 +57,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
+from matcha import _graphs as G
 from matcha import _native as N
 from matcha._abi import AdamWChunk as _AdamWChunk
 from matcha.models.components import _ops as OPS
@@ -80,6 +80,25 @@ def synthetic_batch(B: int, Tx: int, Ty: int, n_feats: int = 80, seed: int = 0, 
     x = x * (pos_x < x_lengths[:, None])
     y = y * (pos_y < y_lengths[:, None, None])
     return {k: v.to(device) for k, v in dict(x=x, x_lengths=x_lengths, y=y, y_lengths=y_lengths).items()}
+
+
+def _total_and_logged(dur, prior, diff, segments: int = 1):
+    """(total = dur + prior + diff, the logged [dur, prior, diff, total] as detached fp32) in one launch on the
+    device; the CPU data-parallel tests drive the loop with a CPU stand-in model.  segments > 1 (merged
+    micro-batches, [segments] tensors): the mean over micro-batches of each one's total / logged vector."""
+    if segments > 1:
+        parts = [OPS.loss_sum(dur[j], prior[j] if torch.is_tensor(prior) else 0, diff[j]) for j in range(segments)]
+        return sum(tp[0] for tp in parts) / segments, sum(tp[1] for tp in parts) / segments
+    if dur.device.type == "cuda":
+        return OPS.loss_sum(dur, prior, diff)
+    total = dur + prior + diff
+    return total, torch.stack([dur, torch.as_tensor(prior), diff, total]).detach().float()
+
+
+# how Trainer._armed arms the data-parallel reducer for a backward
+ARM_OVERLAP = "overlap"  # pack, each bucket's all-reduce forked off as the backward completes it
+ARM_REDUCE_AFTER = "reduce-after"  # pack; the caller reduces after the backward (torch.distributed transport)
+ARM_PACK_ONLY = "pack-only"  # pack, never communicate (a capture's warm-up passes)
 
 
 class _FlatClipAdamW:
@@ -243,9 +262,9 @@ class Trainer:
         self.dp_mode = mode if self.dp else None
         self.reducer = None
         self._recorder = None
-        self._arm = None  # (overlap,) while the reducer is to be armed in the next backward
-        self._graphs = collections.OrderedDict()
-        self._val_graphs = collections.OrderedDict()  # validation_step's captures, an LRU of its own
+        self._arm = None  # an ARM_* mode inside _armed(): the next backward arms the reducer
+        self._graphs = G.GraphCache(cfg.graph_cache)  # captured steps per input-shape key, LRU
+        self._val_graphs = G.GraphCache(cfg.graph_cache)  # validation_step's: it never evicts a train step
         self._best_k = {}  # fit's best checkpoints: file name -> loss/val (saved with every checkpoint)
         # bench.py's N>1 path (matcha/watchdog.py): a host watchdog told of every step / graph key / bucket issue,
         # and device progress markers captured into the step (one after each bucket's all-reduce, one at its end)
@@ -289,6 +308,31 @@ class Trainer:
     def _autocast(self):
         return trainer_precision(self.cfg.precision) if self.dev.type == "cuda" else contextlib.nullcontext()
 
+    def _losses(self, net, batch, out_size):
+        """(dur, prior, diff) of `net` (self.wrapped to train, self.model to validate) on one batch under the
+        trainer's precision context, the batch's "t" / "z" / "out_offset" (the parity tests' CFM randomness and
+        segment windows) and "durations" (a use_precomputed_durations model's) injected."""
+        inject = {k: batch[k] for k in ("t", "z", "out_offset", "durations") if k in batch}
+        if out_size is not None:
+            inject["out_size"] = out_size
+        if batch.get("_segments", 1) > 1:  # merged micro-batches: per-micro-batch losses ([seg] tensors)
+            inject["segments"] = batch["_segments"]
+        with self._autocast():
+            dur, prior, diff, *_ = net(x=batch["x"], x_lengths=batch["x_lengths"], y=batch["y"],
+                                       y_lengths=batch["y_lengths"], **inject)
+        return dur, prior, diff
+
+    @contextlib.contextmanager
+    def _armed(self, mode):
+        """The last micro-batch's backward of the enclosed _fwd_bwd arms the reducer in `mode` (ARM_*): it packs
+        the accumulated gradients (and the logged means) bucket by bucket as the backward produces them."""
+        self._arm = mode
+        try:
+            yield
+        finally:
+            self._arm = None
+            OPS.set_grad_slots(None)  # an aborted backward leaves no slots armed
+
     def _fwd_bwd(self, batches, sync_ctx=None):
         n = len(batches)
         if n > 1 and self._merge_ok(batches):
@@ -300,15 +344,13 @@ class Trainer:
         # (components/_defer.py deferred_grad_sums): needs fresh gradients, which autograd steals (one
         # micro-batch, gradients set to None first), and no DDP hook reading them during the backward
         # (the bucket reducer flushes the queue per bucket)
-        fresh = n == 1 and self.dev.type == "cuda" and all(p.grad is None for p in self.params)
-        defer = fresh and (self.cfg.graph or self.dp_mode != "ddp")
+        fresh = (self.dev.type == "cuda" and all(p.grad is None for p in self.params)
+                 and (self.cfg.graph or self.dp_mode != "ddp"))
         # several micro-batches (accumulate_grad_batches): the FIRST one's gradients are fresh too -- its
         # backward runs deferred (batched weight gradients, flushed when it ends, before the next micro-batch
         # accumulates into them); the later ones accumulate and run per layer
-        self._defer_first = (n > 1 and self.dev.type == "cuda" and all(p.grad is None for p in self.params)
-                             and (self.cfg.graph or self.dp_mode != "ddp"))
-        with deferred_grad_sums(defer):
-            return self._fwd_bwd_body(batches, sync_ctx)
+        with deferred_grad_sums(fresh and n == 1):
+            return self._fwd_bwd_body(batches, sync_ctx, defer_first=fresh and n > 1)
 
     def _merge_ok(self, batches) -> bool:
         """TrainConfig.merge_micro_batches and every micro-batch the same padded shapes (CUDA MatchaTTS)."""
@@ -337,7 +379,6 @@ class Trainer:
         order, ((g_1 + g_2) + g_3) ..., the fp32 adds autograd's AccumulateGrad does -- so the result equals
         the accumulating path's (tests/test_training_gpu.py::test_accumulate_grad_batches_2_vs_torch)."""
         n = len(batches)
-        self._defer_first = False
         logged = None
         stash = []
         for i, batch in enumerate(batches):
@@ -364,43 +405,18 @@ class Trainer:
             p.grad = gk
         return logged / n
 
-    def _fwd_bwd_body(self, batches, sync_ctx=None, div=None):
+    def _fwd_bwd_body(self, batches, sync_ctx=None, div=None, defer_first=False):
         n = len(batches)
         logged = None
         for i, batch in enumerate(batches):
             ctx = sync_ctx(i) if sync_ctx else contextlib.nullcontext()
-            first = deferred_grad_sums(True) if (i == 0 and getattr(self, "_defer_first", False)) \
-                else contextlib.nullcontext()
+            first = deferred_grad_sums(True) if (i == 0 and defer_first) else contextlib.nullcontext()
             with ctx, first:
-                # parity tests' CFM randomness and segment windows
-                # (and a use_precomputed_durations model's durations)
-                inject = {k: batch[k] for k in ("t", "z", "out_offset", "durations") if k in batch}
-                if self.cfg.out_size is not None:
-                    inject["out_size"] = self.cfg.out_size
-                seg = batch.get("_segments", 1)
-                if seg > 1:  # merged micro-batches: per-micro-batch losses ([seg] tensors)
-                    inject["segments"] = seg
-                with self._autocast():
-                    dur, prior, diff, _ = self.wrapped(x=batch["x"], x_lengths=batch["x_lengths"],
-                                                       y=batch["y"], y_lengths=batch["y_lengths"], **inject)
-                # total = dur + prior + diff and the logged [dur, prior, diff, total] in one launch (device
-                # tensors; the CPU data-parallel tests drive this loop with a CPU stand-in model)
-                if seg > 1:  # the mean over micro-batches of each one's total / logged vector
-                    parts = [OPS.loss_sum(dur[j], prior[j] if torch.is_tensor(prior) else 0, diff[j])
-                             for j in range(seg)]
-                    total = sum(tp[0] for tp in parts) / seg
-                    vals = sum(tp[1] for tp in parts) / seg
-                elif dur.device.type == "cuda":
-                    total, vals = OPS.loss_sum(dur, prior, diff)
-                else:
-                    total = dur + prior + diff
-                    vals = torch.stack([dur.detach(), torch.as_tensor(prior).detach(), diff.detach(),
-                                        total.detach()]).float()
+                losses = self._losses(self.wrapped, batch, self.cfg.out_size)
+                total, vals = _total_and_logged(*losses, segments=batch.get("_segments", 1))
                 logged = vals if logged is None else logged + vals
                 if i == n - 1 and self._arm is not None:
-                    # the last micro-batch's backward exchanges the accumulated gradients (and the logged
-                    # means) bucket by bucket as backward produces them ("local": pack only, no collective)
-                    self.reducer.arm(logged / n, overlap=self._arm is True, comm=self._arm != "local")
+                    self.reducer.arm(logged / n, overlap=self._arm == ARM_OVERLAP, comm=self._arm != ARM_PACK_ONLY)
                 d = div if div is not None else n
                 (total / d if d > 1 else total).backward()
         return logged / n if n > 1 else logged
@@ -489,12 +505,8 @@ class Trainer:
             self.reducer.attach_views()
             logged = self.reducer.scalars().clone()
         elif self.dp_mode == "buckets":
-            self._arm = True
-            try:
+            with self._armed(ARM_OVERLAP):
                 self._fwd_bwd(batches)
-            finally:
-                self._arm = None
-                OPS.set_grad_slots(None)  # an aborted backward leaves no slots armed
             self.reducer.finish()
             logged = self.reducer.scalars().clone()
         else:
@@ -534,12 +546,8 @@ class Trainer:
                         self.reducer.views[i].copy_(p.grad)
                     self.reducer.attach_views()
                 elif self.dp:
-                    self._arm = "local"
-                    try:
+                    with self._armed(ARM_PACK_ONLY):
                         self._fwd_bwd(static)
-                    finally:
-                        self._arm = None
-                        OPS.set_grad_slots(None)  # an aborted backward leaves no slots armed
                     self.reducer.finish()
                 else:
                     self._fwd_bwd(static)
@@ -555,38 +563,29 @@ class Trainer:
         if self.dp:
             self.reducer.attach_views()
             self.optimizer.bind_grads()  # the table points at the flat buffer's views (fixed addresses)
-        # with a process group up, its watchdog thread polls the events of earlier collectives (e.g. the
-        # eager all-reduce of the torch.distributed transport) at any time; in the default "global"
-        # capture mode such a query from another thread invalidates the capture and aborts the
-        # process.  "thread_local" restricts only this thread (the autograd thread's launches still go
-        # to the capturing stream and its allocations to the graph pool)
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        e["g_fb"] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(e["g_fb"], capture_error_mode=mode):
+
+        def fwd_bwd():
             for p in self.params:
                 p.grad = None  # autograd hands over each fresh gradient: no accumulate kernels
-            if self.dp:
-                self._arm = overlap
-                try:
-                    e["logged"] = self._fwd_bwd(static)
-                finally:
-                    self._arm = None
-                    OPS.set_grad_slots(None)  # an aborted backward leaves no slots armed
-                self.reducer.finish()  # joins the forked all-reduces; .grad -> flat views
-                if overlap:
-                    self._clip_and_update()
-                    if self.progress is not None:  # the device's "step done" marker, a node of the graph
-                        self.progress.mark_step(torch.cuda.current_stream(self.dev))
-            else:
-                e["logged"] = self._fwd_bwd(static)
+            if not self.dp:
+                return self._fwd_bwd(static)
+            with self._armed(ARM_OVERLAP if overlap else ARM_REDUCE_AFTER):
+                logged = self._fwd_bwd(static)
+            self.reducer.finish()  # joins the forked all-reduces; .grad -> flat views
+            if overlap:
+                self._clip_and_update()
+                if self.progress is not None:  # the device's "step done" marker, a node of the graph
+                    self.progress.mark_step(torch.cuda.current_stream(self.dev))
+            return logged
+
+        # (the warm-up above is the step's own: passes=0)
+        e["g_fb"], e["logged"] = G.capture(fwd_bwd, self.dev, passes=0)
         e["fb_grads"] = [p.grad for p in gparams]  # graph-pool outputs, kept alive with the graph
         e["g_opt"] = None
         if not overlap:
             if not self.dp:  # the optimizer graph's table points at the (fixed) graph-pool gradients
                 self.optimizer.bind_grads()
-            e["g_opt"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(e["g_opt"], pool=e["g_fb"].pool(), capture_error_mode=mode):
-                self._clip_and_update()
+            e["g_opt"], _ = G.capture(self._clip_and_update, self.dev, passes=0, pool=e["g_fb"].pool())
         e["opt_keep"] = (self.optimizer._table, self.optimizer._ws)  # the captured kernels read these
         e["overlap"] = overlap
         return e
@@ -626,14 +625,7 @@ class Trainer:
         if self.watchdog is not None:
             self.watchdog.note(graph_key="|".join(f"B{b['x'].shape[0]}xTx{b['x'].shape[1]}xTy{b['y'].shape[-1]}"
                                                   for b in batches), graph_cached=key in self._graphs)
-        e = self._graphs.get(key)
-        if e is None:
-            e = self._graph_capture(batches)
-            self._graphs[key] = e
-            while len(self._graphs) > max(1, self.cfg.graph_cache):
-                self._graphs.popitem(last=False)  # least recently used shape
-        else:
-            self._graphs.move_to_end(key)
+        e = self._graphs.lookup(key, lambda: self._graph_capture(batches))
         for b, s in zip(batches, e["static"]):
             for k, v in s.items():
                 if b[k] is not v:
@@ -663,12 +655,10 @@ class Trainer:
         r.tail_events = ev
         for p in self.params:
             p.grad = None
-        self._arm = True
         try:
-            self._fwd_bwd(self._agree_shapes(batches))
+            with self._armed(ARM_OVERLAP):
+                self._fwd_bwd(self._agree_shapes(batches))
         finally:
-            self._arm = None
-            OPS.set_grad_slots(None)
             r.tail_events = None
         r.finish()
         torch.cuda.synchronize(self.dev)
@@ -716,17 +706,8 @@ class Trainer:
         """[dur, prior, diff, total] of one batch: the model's forward as the train step calls it (the batch's
         "t" / "z" / "out_offset" / "durations" injected) under the trainer's precision context.  out_size as
         get_losses applies it: TrainConfig.out_size, else the model's own."""
-        inject = {k: batch[k] for k in ("t", "z", "out_offset", "durations") if k in batch}
         out_size = self.cfg.out_size if self.cfg.out_size is not None else getattr(self.model, "out_size", None)
-        if out_size is not None:
-            inject["out_size"] = out_size
-        with self._autocast():
-            dur, prior, diff, *_ = self.model(x=batch["x"], x_lengths=batch["x_lengths"], y=batch["y"],
-                                              y_lengths=batch["y_lengths"], **inject)
-        if dur.device.type == "cuda":
-            return OPS.loss_sum(dur, prior, diff)[1]
-        total = dur + prior + diff
-        return torch.stack([dur, torch.as_tensor(prior), diff, total]).float()
+        return _total_and_logged(*self._losses(self.model, batch, out_size))[1]
 
     def _val_graph_step(self, batch):
         """validation_step on the GPU in graph mode: the forward captured once per input-shape key (an LRU of its
@@ -734,29 +715,17 @@ class Trainer:
         from static input buffers.  No gradient deferral is open here, so MatchaTTS.forward takes no prefetch
         fork: the capture has one stream."""
         key = tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(batch.items()))
-        e = self._val_graphs.get(key)
-        if e is None:
+
+        def build():
             static = {k: v.clone() for k, v in batch.items()}
-            side = torch.cuda.Stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):  # warm-up: allocator pools, pack plans, lazy loads
-                for _ in range(2):
-                    self._val_losses(static)
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=mode):
-                out = self._val_losses(static)
-            e = self._val_graphs[key] = {"g": g, "static": static, "out": out}
-            while len(self._val_graphs) > max(1, self.cfg.graph_cache):
-                self._val_graphs.popitem(last=False)
-        else:
-            self._val_graphs.move_to_end(key)
-        for k, v in e["static"].items():
+            return static, *G.capture(lambda: self._val_losses(static), self.dev, passes=2)
+
+        static, g, out = self._val_graphs.lookup(key, build)
+        for k, v in static.items():
             if batch[k] is not v:
                 v.copy_(batch[k], non_blocking=True)
-        e["g"].replay()
-        return e["out"].clone()  # the next replay overwrites the graph's own output
+        g.replay()
+        return out.clone()  # the next replay overwrites the graph's own output
 
     def validation_step(self, batch: dict) -> torch.Tensor:
         """The reference's validation_step (baselightningmodule.py:164-202) on one batch: the device tensor

@@ -31,6 +31,7 @@ import math
 import numpy as np
 import torch
 
+from matcha import _graphs as G
 from matcha import _native as N
 from matcha._abi import MTTS_GL_HOP as GL_HOP, MTTS_GL_NFFT as GL_NFFT  # the one STFT geometry the kernels serve
 
@@ -346,9 +347,9 @@ class GriffinLim:
 
     One run is a synthesis launch (phase update + inverse FFT + window) and an analysis launch (overlap-add gather +
     window + FFT) per iteration, plus the first synthesis and the final gather; it is captured once per
-    (B, F, n_iter) into a HIP graph (at most 8 cached) and replayed; under an outer capture, or with ``graph =
-    False``, the same launches run eagerly.  With ``rand_init`` the initial phase has real and imaginary parts uniform
-    in [0, 1) -- not unit magnitude; torchaudio's behaviour -- drawn with torch's generator before the replay;
+    (B, F, n_iter) into a HIP graph (the 8 most recently used stay cached) and replayed; under an outer capture, or
+    with ``graph = False``, the same launches run eagerly.  With ``rand_init`` the initial phase has real and
+    imaginary parts uniform in [0, 1) -- not unit magnitude; torchaudio's behaviour -- drawn with torch's generator before the replay;
     ``rand_init=False`` starts from the phase 1 + 0i in every bin, as torchaudio does, and is repeatable unseeded;
     ``angles`` (complex [B, n_fft//2 + 1, F]) injects it instead.
 
@@ -374,7 +375,7 @@ class GriffinLim:
             raise ValueError(f"bad n_iter / power: {n_iter}, {power}")
         self.n_fft, self.n_iter, self.win_length, self.hop_length = n_fft, int(n_iter), win_length, hop_length
         self.power, self.momentum, self.length, self.rand_init = float(power), float(momentum), length, bool(rand_init)
-        self._graphs = {}
+        self._graphs = G.GraphCache(self._GRAPH_CACHE_MAX)
 
     def to(self, *args, **kwargs):
         return self
@@ -420,21 +421,18 @@ class GriffinLim:
     def _run(self, B, F, device, *, spec=None, mel=None, inverse_mel=None, angles=None):
         if self.graph and not torch.cuda.is_current_stream_capturing():
             key = (B, F, self.n_iter, str(device), inverse_mel is not None)
-            st = self._graphs.get(key)
-            if st is None:
-                if len(self._graphs) >= self._GRAPH_CACHE_MAX:
-                    self._graphs.pop(next(iter(self._graphs)))
+
+            def build():
                 st = _GLState(B, F, device, inverse_mel.n_mels if inverse_mel is not None else None)
-                cur = torch.cuda.current_stream(device)
-                side = torch.cuda.Stream(device)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):  # warm-up on the zeroed buffers: lazy code-object loads
-                    self._launch(st, B, F, device, inverse_mel, n_iter=min(self.n_iter, 2))
-                cur.wait_stream(side)
-                st.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(st.graph):
-                    self._launch(st, B, F, device, inverse_mel)
-                self._graphs[key] = st
+
+                def launch(n_iter=None):
+                    self._launch(st, B, F, device, inverse_mel, n_iter)
+
+                # the warm-up runs on the zeroed buffers, shortened: it only has to load the code objects
+                st.graph, _ = G.capture(launch, device, warmup=lambda: launch(min(self.n_iter, 2)))
+                return st
+
+            st = self._graphs.lookup(key, build)
             self._fill(st, spec, mel, angles)
             st.graph.replay()
             return st.wav.clone()

@@ -149,6 +149,10 @@ def test_graph_replay_equals_eager_and_caches_per_shape():
     for F in range(10, 20):  # the cache is bounded
         gl(torch.rand(1, 513, F, device=DEV))
     assert len(gl._graphs) == GriffinLim._GRAPH_CACHE_MAX == 8
+    first, second = list(gl._graphs)[:2]  # ... and evicts the least recently used shape, not the oldest capture
+    gl(torch.rand(1, 513, first[1], device=DEV))
+    gl(torch.rand(1, 513, 20, device=DEV))
+    assert first in gl._graphs and second not in gl._graphs and len(gl._graphs) == 8
 
 
 def test_rand_init_draws_from_torchs_generator():
