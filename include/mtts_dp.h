@@ -36,8 +36,9 @@ int mtts_dp_rccl_version(void);
 /* Device-side progress for a host watchdog (bench.py's N>1 path): *host_out = nslots int32 in coherent
  * host-mapped memory, zeroed, readable at any time without synchronising the device.
  * mtts_dp_progress_mark is stream-ordered and capturable: tag < 0 adds one to the device's step count and
- * writes it to host[0]; tag >= 0 writes steps * 256 + tag to host[slot] (slot >= 1; the reducer marks
- * bucket k done with tag k + 1 after its all-reduce).  No reference counterpart (the reference has no
+ * writes it to host[0]; tag in 0..255 writes steps * 256 + tag to host[slot] (slot >= 1; the reducer marks
+ * bucket k done with tag k + 1 after its all-reduce: at most 255 buckets, and 2^23 steps before the int32
+ * overflows; one word so the host never reads a torn pair).  No reference counterpart (the reference has no
  * multi-GPU step; DDP's own watchdog is torch's ProcessGroupNCCL timeout). */
 int mtts_dp_progress_create(int32_t nslots, void **handle_out, int32_t **host_out);
 int mtts_dp_progress_mark(void *handle, int32_t slot, int32_t tag, void *hip_stream);

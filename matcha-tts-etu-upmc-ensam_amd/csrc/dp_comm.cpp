@@ -147,6 +147,9 @@ extern "C" int mtts_dp_rccl_version(void) {
 // stream-ordered and capturable -- inside the step's graph after each bucket's all-reduce (reducer stream) and at
 // the end of the step (main stream).  Slot 0 = steps the device has completed (a device-side counter incremented
 // by the step-end mark), slot s > 0 = steps * 256 + tag of the last mark on that slot (tag = bucket index + 1).
+// One int32 per mark on purpose: a (step, tag) pair in two slots would be two stores the host can read torn.  The
+// tag has the low 8 bits (0 = nothing marked yet, 1..255 = buckets 0..254; a larger tag is refused), the step
+// field the other 23 value bits: 2^23 steps before the int32 overflows.
 namespace {
 struct Progress {
     int32_t *host = nullptr;  // hipHostMalloc(mapped | coherent): the watchdog reads it
@@ -191,6 +194,7 @@ extern "C" int mtts_dp_progress_create(int32_t nslots, void **handle_out, int32_
 extern "C" int mtts_dp_progress_mark(void *handle, int32_t slot, int32_t tag, void *hip_stream) {
     Progress *pr = static_cast<Progress *>(handle);
     MTTS_CHECK_ARG(pr && slot >= 0 && slot < pr->nslots && (tag < 0 || slot > 0), "dp_progress_mark: bad args");
+    MTTS_CHECK_ARG(tag <= 255, "dp_progress_mark: tag above 255 (it would spill into the step field)");
     hipLaunchKernelGGL(progress_mark_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(hip_stream), pr->dev,
                        pr->host, slot, tag);
     return mtts::check_launch("progress_mark_kernel");

@@ -258,6 +258,17 @@ class GradBucketReducer:
         if self.watchdog is not None:
             self.watchdog.beat(bucket_returned=k)
 
+    def disarm(self) -> None:
+        """After an armed forward / backward that raised: the hooks go quiet, the grad slots are cleared and a
+        later finish() is a no-op -- instead of issuing the remaining buckets' collectives from whatever
+        backward or finish() comes next."""
+        from matcha.models.components import _ops as OPS
+
+        self.armed = False
+        OPS.set_grad_slots(None)
+        self._pending_scalars = None
+        self.grad_refs = None
+
     def warm(self) -> None:
         """One eager all-reduce per bucket span on every rank (all ranks call this together, when the
         reducer is built): RCCL sets up its connections for each message size on first use, which must not

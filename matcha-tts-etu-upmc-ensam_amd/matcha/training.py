@@ -329,6 +329,12 @@ class Trainer:
         self._arm = mode
         try:
             yield
+        except BaseException:
+            # an aborted forward / backward leaves the reducer disarmed: its hooks issue nothing in a later
+            # backward and a later finish() returns at once (it would otherwise issue the remaining buckets)
+            if self.reducer is not None:
+                self.reducer.disarm()
+            raise
         finally:
             self._arm = None
             OPS.set_grad_slots(None)  # an aborted backward leaves no slots armed
@@ -478,7 +484,17 @@ class Trainer:
             first_enc = next((p for p in order if id(p) in enc_ids), None)
             if first_enc is not None:
                 seams, mb = (first_enc,), max(mb, self.cfg.seam_bucket_mb)
-        self.reducer = DP.GradBucketReducer(order, comm, mb, self.dev, seams=seams)
+        reducer = DP.GradBucketReducer(order, comm, mb, self.dev, seams=seams)
+        # the device's bucket mark holds the bucket tag in 8 bits (matcha/watchdog.py): refused here, not in a
+        # hook in the middle of a backward
+        limit = getattr(self.progress, "MAX_BUCKETS", None)
+        if limit is not None and len(reducer.buckets) > limit:
+            reducer.remove()
+            if hasattr(comm, "close"):
+                comm.close()
+            raise ValueError(f"data parallel: the bucket layout has {len(reducer.buckets)} buckets, the device "
+                             f"progress markers encode at most {limit} (raise bucket_mb)")
+        self.reducer = reducer
         self.reducer.watchdog, self.reducer.progress = self.watchdog, self.progress
         if isinstance(self.optimizer, _FlatClipAdamW):  # the mean over ranks rides in the fused optimizer step
             self.optimizer.grad_scale = comm.post_scale
@@ -652,15 +668,15 @@ class Trainer:
         if r is None or not self.dp or self.dev.type != "cuda" or not r.comm.capturable:
             return None
         ev = {k: torch.cuda.Event(enable_timing=True) for k in ("start", "end", "bwd_end")}
-        r.tail_events = ev
         for p in self.params:
             p.grad = None
+        r.tail_events = ev
         try:
-            with self._armed(ARM_OVERLAP):
+            with self._armed(ARM_OVERLAP):  # (a forward / backward that raises leaves the reducer disarmed)
                 self._fwd_bwd(self._agree_shapes(batches))
+            r.finish()  # records "bwd_end": while tail_events is still set
         finally:
             r.tail_events = None
-        r.finish()
         torch.cuda.synchronize(self.dev)
         ar = ev["start"].elapsed_time(ev["end"])
         exposed = max(0.0, ev["bwd_end"].elapsed_time(ev["end"]))

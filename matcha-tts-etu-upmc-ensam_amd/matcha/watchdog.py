@@ -25,9 +25,12 @@ from matcha import _native as N
 
 class DeviceProgress:
     """Host-mapped progress slots written by the device in stream order (include/mtts_dp.h).  Slot 0: steps the
-    device completed; slot 1: steps * 256 + (index + 1) of the last bucket whose all-reduce completed."""
+    device completed; slot 1: steps * 256 + (index + 1) of the last bucket whose all-reduce completed -- ONE int32,
+    so the host never reads a torn (step, bucket) pair: the tag takes the low 8 bits (MAX_BUCKETS buckets, tag 0
+    is "none yet") and the step field the rest (2^23 steps before the int32 overflows)."""
 
     SLOTS = 2
+    MAX_BUCKETS = 255  # tags 1..255; Trainer._ensure_reducer refuses a layout with more
 
     def __init__(self):
         self._h = ctypes.c_void_p()
@@ -39,6 +42,9 @@ class DeviceProgress:
         N.check(N.lib().mtts_dp_progress_mark(self._h, 0, -1, stream.cuda_stream), "mtts_dp_progress_mark")
 
     def mark_bucket(self, k: int, stream) -> None:
+        if not 0 <= k < self.MAX_BUCKETS:  # before any launch: tag k + 1 would spill into the step field
+            raise ValueError(f"DeviceProgress.mark_bucket: bucket {k} outside 0..{self.MAX_BUCKETS - 1} "
+                             f"(the mark encodes at most {self.MAX_BUCKETS} buckets)")
         N.check(N.lib().mtts_dp_progress_mark(self._h, 1, k + 1, stream.cuda_stream), "mtts_dp_progress_mark")
 
     def read(self) -> dict:

@@ -194,3 +194,99 @@ def test_bucket_layout_cuts_at_seams():
     assert any(s < 6 < e for s, e in plain.buckets)
     r.remove()
     plain.remove()
+
+
+class SwitchTTS(TinyTTS):
+    """TinyTTS with a residual submodule that ``skip_extra`` leaves out of the forward: its parameters then get
+    no gradient."""
+
+    def __init__(self):
+        super().__init__()
+        self.extra = torch.nn.Linear(80, 80)
+        self.skip_extra = False
+
+    def forward(self, x, x_lengths, y, y_lengths, out_size=None, cond=None, durations=None):
+        mu = self.proj(self.emb(x)).mean(1)
+        if not self.skip_extra:
+            mu = mu + self.extra(mu)
+        tgt = y.mean(-1)
+        return (mu ** 2).mean() * 0.1, ((mu - tgt) ** 2).mean(), (mu.abs()).mean() * 0.01, None
+
+
+@pytest.fixture
+def gloo_world1():
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    try:
+        yield
+    finally:
+        dist.destroy_process_group()
+
+
+def test_finish_issues_every_bucket_when_a_parameter_got_no_gradient(gloo_world1):
+    """GradBucketReducer.finish() after a backward that left a parameter without a gradient: the buckets that
+    never became ready are issued all the same (missing gradients as zeros), so this rank stays in its peers'
+    collective sequence, and only then the step raises; the reducer is disarmed, the grad slots are cleared and
+    no update was applied."""
+    from matcha.models.components import _ops as OPS
+    from matcha.training import TrainConfig, Trainer
+
+    torch.manual_seed(0)
+    model = SwitchTTS()
+    tr = Trainer(model, TrainConfig(precision="32-true", graph=False, dp="buckets", force_dp=True, bucket_mb=0.001))
+    for s in range(2):  # the recording step, then one overlapped step
+        assert torch.isfinite(tr.step(_batches(0, 1))).all()
+    r = tr.reducer
+    assert len(r.buckets) >= 2 and r._issued == len(r.buckets) and r.armed is False
+    before = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    issued = []
+    real_issue = r._issue
+    r._issue = lambda k: (issued.append(k), real_issue(k))[1]
+    model.skip_extra = True
+    with pytest.raises(RuntimeError, match="got no gradient"):
+        tr.step(_batches(0, 1))
+    assert issued == list(range(len(r.buckets)))  # each bucket once, in index order
+    assert r._issued == len(r.buckets)
+    assert r.armed is False
+    assert OPS._GRAD_SLOTS["map"] is None
+    extra = {id(p) for p in model.extra.parameters()}
+    missing = [i for i, p in enumerate(r.params) if id(p) in extra]
+    assert len(missing) == 2
+    for i in missing:  # packed as zeros
+        assert int(r.views[i].count_nonzero()) == 0
+    for k, v in model.state_dict().items():
+        assert torch.equal(v, before[k]), k
+
+
+def test_bucket_count_above_the_progress_limit_is_refused_at_construction(gloo_world1):
+    """Trainer._ensure_reducer with device progress markers wired: a bucket layout the 8-bit bucket tag cannot
+    encode raises when the reducer is built (naming both numbers), not from a hook inside a backward."""
+    from matcha.training import TrainConfig, Trainer
+    from matcha.watchdog import DeviceProgress
+
+    assert DeviceProgress.MAX_BUCKETS == 255
+
+    class StubProgress:
+        MAX_BUCKETS = 1
+        marks = []
+
+        def mark_bucket(self, k, stream):
+            self.marks.append(("bucket", k))
+
+        def mark_step(self, stream):
+            self.marks.append(("step",))
+
+    torch.manual_seed(0)
+    model = TinyTTS()
+    tr = Trainer(model, TrainConfig(precision="32-true", graph=False, dp="buckets", force_dp=True, bucket_mb=0.001))
+    tr.progress = StubProgress()
+    with pytest.raises(ValueError, match=r"\b3 buckets\b.*\bat most 1\b"):
+        tr.step(_batches(0, 1))
+    assert tr.reducer is None and StubProgress.marks == []
+    # neither the recorder's nor the refused reducer's hooks stay on the parameters
+    assert all(not getattr(p, "_post_accumulate_grad_hooks", None) for p in model.parameters())
+    StubProgress.MAX_BUCKETS = 3  # the layout's own count is accepted
+    tr = Trainer(TinyTTS(), TrainConfig(precision="32-true", graph=False, dp="buckets", force_dp=True, bucket_mb=0.001))
+    tr.progress = StubProgress()
+    tr.step(_batches(0, 1))
+    assert len(tr.reducer.buckets) == 3 and tr.reducer.progress is tr.progress
