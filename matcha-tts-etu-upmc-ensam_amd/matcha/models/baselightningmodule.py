@@ -83,6 +83,18 @@ class BaseLightningClass(nn.Module):
     def log(self, name, value, **kwargs):  # Lightning API: recorded for the driver to reduce/print
         self.__dict__.setdefault("_logged", {})[name] = value
 
+    def log_dict(self, dictionary, **kwargs):  # Lightning API: one log() per item
+        for name, value in dictionary.items():
+            self.log(name, value, **kwargs)
+
+    def on_before_optimizer_step(self, optimizer):
+        """baselightningmodule.py:244-245: every parameter's gradient 2-norm and their total, logged as
+        ``grad_norm/grad_2.0_norm/<parameter name>`` and ``grad_norm/grad_2.0_norm_total``.  (A driver that
+        wants the log calls this between backward and the optimizer step; matcha.training.Trainer does not.)"""
+        from matcha.utils.grad_norm import grad_norm
+
+        self.log_dict({f"grad_norm/{k}": v for k, v in grad_norm(self, norm_type=2).items()})
+
     def configure_optimizers(self) -> dict[str, Any]:
         """baselightningmodule.py:57-92: AdamW(1e-4, (0.9, 0.999), wd 1e-6) + per-epoch cosine
         annealing (T_max 1000, eta_min 1e-6)."""
